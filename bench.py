@@ -2,6 +2,13 @@
 
   python bench.py [--gpus N --steps K --warmup W]                   # N = 1 here
   torchrun --nproc-per-node N bench.py --gpus N ...                 # driver, N > 1
+  ... --dump-outputs DIR                                            # + the last step's field as .npy
+  ... --full                                                        # + every secondary measurement
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything under "Also
+reported" below, the extra_configs, and at N > 1 the field checks against the single-domain solve
+run only with --full (where --no-cpu-baseline / --no-path / --no-timing / --no-extra / --extras
+pick among them).
 
 Workload (BASELINE.json configs): N = 1 -> config[1], a 4096 x 4096 DEM-derived cost raster
 (terrain.py: fractal DEM seed 42 + the planner's cost recipe), single goal at the centre,
@@ -14,7 +21,7 @@ growing raster instead.  A "step" = one full solve of the whole raster (T init -
 inputs resident in HBM.  value = cells of the global raster x steps / max-over-ranks wall time
 (Gcells/s).
 
-Also reported: roofline of the dominant kernel (fim2d_persist_kernel, one launch per solve:
+Also reported (--full): roofline of the dominant kernel (fim2d_persist_kernel, one launch per solve:
 hipEvents around it on the solver stream over the timed region; algorithmic bytes = full tile
 visits x 50176 B + in-place passes x 17408 B in fp32, twice that in fp64), ms-to-path
 (host cost -> host path, N = 1), and the CPU baseline (oracle C heap FMM, 1 thread, N = 1).
@@ -67,16 +74,25 @@ def main():
     ap.add_argument("--dd", choices=["live", "rounds"], default="live",
                     help="N > 1: live persistent launches + IPC halo rounds, or relaunch-per-round over RCCL")
     ap.add_argument("--sync-every", type=int, default=8)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-path", action="store_true")
-    ap.add_argument("--no-timing", action="store_true", help="skip per-launch events (roofline)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / C5 secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: roofline pass, ms-to-path, extra_configs, CPU "
+                         "baseline, and at N > 1 the checks against the single-domain solve")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write the arrival field of the last step to DIR/T.npy (-1 where "
+                         "unreached) and DIR/reached.npy (N > 1: every rank its block, *_rank<r>.npy); a fixed "
+                         "seeded sample of the cells when the field is larger than the dump budget")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-path", action="store_true", help="--full: skip ms-to-path")
+    ap.add_argument("--no-timing", action="store_true", help="--full: skip per-launch events (roofline)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the C3 / C5 secondary measurements")
     ap.add_argument("--extra-steps", type=int, default=5)
     ap.add_argument("--extras", type=str, default="all",
                     help="comma list of extra_configs to run at N = 1 (C2_other,C3,C5,costmap,C4_1gpu,arm) or all")
     ap.add_argument("--pmc-traffic", type=str, default=None,
                     help="PMC summary (tools/pmc_traffic.py); default profiles/pmc_traffic_<dtype>.json")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_cpu_baseline = args.no_path = args.no_timing = args.no_extra = True
     f64 = args.dtype == "f64"
     tdt = torch.float64 if f64 else torch.float32
     edt = L.EIK_F64 if f64 else L.EIK_F32
@@ -203,10 +219,12 @@ def main():
 
     # 1) the measurement: no per-launch instrumentation inside the timed region
     el, _, _, _, _, _ = timed(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, T, rank, world)
     # 2) the same K steps again with a hipEvent pair around every sweep launch (roofline)
     el_i, visits, passes, fresh, sweep_ms, iters = (0.0, 0, 0, 0, 0.0, 0) if args.no_timing else timed(True)
 
-    if world > 1:  # the halo transport delivered every final edge (a wrong field cannot pass)
+    if world > 1 and args.full:  # the halo transport delivered every final edge (a wrong field cannot pass)
         dd_ok = dd.halo_consistent(blk, T, ghost, group=ctrl)
         # and the assembled field is the single-domain one: every rank solves the whole raster on
         # its own GPU and compares its block (no gather), then -- on RCCL -- one untimed solve of
@@ -275,16 +293,18 @@ def main():
             "H": H, "W": W, "split": f"{px}x{py}", "block": [blk.h, blk.w], "goal": list(goal_g), "tile": 64,
             "parallelism": "single-gpu" if world == 1 else f"domain-decomposition {px}x{py}",
         },
-        "roofline": roof,
     }
+    if args.full:
+        out["roofline"] = roof
     if world > 1:
         out["config"]["dd_mode"] = dd_mode + (" (shm vote)" if dd_mode == "live" and vote is not None else "")
         out["config"]["halo_transport"] = ("hipIpc peer stores (xGMI) + node vote" if dd_mode == "live"
                                            else "RCCL batch_isend_irecv + all_reduce")
-        out["config"]["dd_halo_consistent"] = dd_ok
-        out["config"].update(dd_check)
+        if args.full:
+            out["config"]["dd_halo_consistent"] = dd_ok
+            out["config"].update(dd_check)
         # every rank's work per solve (the decomposition's total against the single-domain solve's)
-        if not args.no_timing:
+        if args.full and not args.no_timing:
             mine = torch.tensor([visits, passes, fresh, blk.h * blk.w], dtype=torch.float64) / \
                 torch.tensor([args.steps, args.steps, args.steps, 1], dtype=torch.float64)
             allr = [torch.zeros_like(mine) for _ in range(world)]
@@ -357,6 +377,30 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 48 * 10 ** 6  # bytes over all ranks' files (the files of one run stay under 64 MB)
+
+
+def dump_outputs(d, T, rank, world):
+    """The arrival field the last timed step left in T, as two finite .npy arrays of one shape:
+    T.npy (the field's dtype) holds the arrival times, with -1 where the solver left +inf (cells the
+    front never reaches: obstacles, the map border); reached.npy (float32) is 1 where the time is
+    finite and 0 there.  Whole when both fit this rank's share of DUMP_BUDGET, else the cells at a
+    fixed sample of flat indices (numpy generator seed 0, sorted -- the same cells in every run of
+    the same arguments).  The inputs are the same bits from run to run; the solver's tile order is
+    not, so two runs' fields agree to rounding (~1e-15 relative in fp64), not bit for bit."""
+    os.makedirs(d, exist_ok=True)
+    n = T.numel()
+    k = DUMP_BUDGET // world // (T.element_size() + 4)
+    t = T
+    if n > k:
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        t = T.reshape(-1)[torch.from_numpy(idx).to(T.device)]
+    unreached = torch.isposinf(t)
+    sfx = "" if world == 1 else f"_rank{rank}"
+    np.save(os.path.join(d, f"T{sfx}.npy"), torch.where(unreached, torch.full_like(t, -1.0), t).cpu().numpy())
+    np.save(os.path.join(d, f"reached{sfx}.npy"), (~unreached).float().cpu().numpy())
 
 
 def ms_to_path(cost, ctx, fim, dev, stream, goal, edt, start=(256, 256), reps=3):

@@ -6,7 +6,7 @@ for i in $(seq 1 ${REPS:-2}); do
   for v in "${VS[@]}"; do
     d=${v%%|*}; opt=${v#*|}
     f="$O/ab2_${d}_${opt//[^A-Za-z0-9]/_}.json"
-    EIKONAL_LIB=planning-motion_planning_amd/$d/libeikonal.so EIK_OPTIONS="$opt" timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > "$f" 2> $O/ab2.err || { echo "bench $v rc=$?"; tail -n 20 $O/ab2.err; exit 1; }
+    EIKONAL_LIB=planning-motion_planning_amd/$d/libeikonal.so EIK_OPTIONS="$opt" timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > "$f" 2> $O/ab2.err || { echo "bench $v rc=$?"; tail -n 20 $O/ab2.err; exit 1; }
     python - "$f" "$v" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

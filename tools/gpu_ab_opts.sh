@@ -6,7 +6,7 @@ IFS='|' read -ra VARIANTS <<< "${OPTS:--}"
 for i in 1 2; do
   for j in "${!VARIANTS[@]}"; do
     v="${VARIANTS[$j]}"; [ "$v" = "-" ] && v=""
-    EIK_OPTIONS="$v" timeout -k 10 300 python bench.py --no-cpu-baseline "$@" > $O/abo_$j.json 2> $O/abo_$j.err || { echo "bench [$v] rc=$?"; tail -n 20 $O/abo_$j.err; exit 1; }
+    EIK_OPTIONS="$v" timeout -k 10 300 python bench.py --full --no-cpu-baseline "$@" > $O/abo_$j.json 2> $O/abo_$j.err || { echo "bench [$v] rc=$?"; tail -n 20 $O/abo_$j.err; exit 1; }
     python - "$j" "$v" <<'PY'
 import json, sys
 d = json.load(open(f"gpurun_out/abo_{sys.argv[1]}.json"))

@@ -10,7 +10,7 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0
 R=${ROUND:-r03}
 for n in ${NS:-2 4 8}; do
   EIK_BENCH_SHARED_GPU=1 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-      --master-addr 127.0.0.1 --master-port $((29700 + n)) bench.py --gpus $n --steps ${STEPS:-3} --warmup 1 \
+      --master-addr 127.0.0.1 --master-port $((29700 + n)) bench.py --full --gpus $n --steps ${STEPS:-3} --warmup 1 \
       ${BENCH_ARGS:-} > gpurun_out/${R}_c4_rehearsal_n$n.log 2>&1 || { echo "n=$n rc=$?"; tail -40 gpurun_out/${R}_c4_rehearsal_n$n.log; exit 1; }
   grep '^{' gpurun_out/${R}_c4_rehearsal_n$n.log | tail -1
 done
