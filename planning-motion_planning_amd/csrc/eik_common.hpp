@@ -294,6 +294,25 @@ __device__ __forceinline__ double wave_shr1_umin_id(double v) {
     return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
+// Whole-wave reduction of a 32-bit value by an idempotent op (min, or) on the DPP path, every lane
+// active: a butterfly inside each row of 16 (quad_perm xor 1, xor 2, row_half_mirror, row_mirror),
+// then row_bcast15 into rows 1 and 3 and row_bcast31 into rows 2 and 3 -- lane 63 holds the wave's
+// result, returned wave-uniform.  (A lane the DPP control leaves out combines with its own value,
+// which an idempotent op ignores.)  Ten VALU instructions once the combiner folds the moves; the
+// per-lane LDS atomics it replaces compile to a serial loop over the active lanes.
+template <class Op>
+__device__ __forceinline__ unsigned wave_reduce_idem(unsigned v, Op op) {
+#define EIK_DPP_STEP(ctrl, rows) v = op(v, (unsigned)__builtin_amdgcn_update_dpp((int)v, (int)v, ctrl, rows, 0xF, false))
+    EIK_DPP_STEP(0xB1, 0xF);   // quad_perm [1,0,3,2]
+    EIK_DPP_STEP(0x4E, 0xF);   // quad_perm [2,3,0,1]
+    EIK_DPP_STEP(0x141, 0xF);  // row_half_mirror
+    EIK_DPP_STEP(0x140, 0xF);  // row_mirror
+    EIK_DPP_STEP(0x142, 0xA);  // row_bcast15 -> rows 1, 3
+    EIK_DPP_STEP(0x143, 0xC);  // row_bcast31 -> rows 2, 3
+#undef EIK_DPP_STEP
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
+}
+
 // LDS atomic min on a non-negative float/double (IEEE order == unsigned-integer order for x >= 0).
 __device__ __forceinline__ void lds_min(float* p, float v) {
     atomicMin(reinterpret_cast<unsigned int*>(p), __float_as_uint(v));

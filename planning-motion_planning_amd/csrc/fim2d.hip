@@ -47,16 +47,13 @@ __device__ __forceinline__ R stage_cost(R c) {
     else return c;
 }
 
-// EIK_EDGE_FIRST (see the write-back in process_tile): measured and OFF -- C2 2-7 % slower in fp64
+// (EIK_EDGE_FIRST, rounds 3-5, measured and removed -- code in commit 39cf948 and before: only the
+// tile's edge cells -- the values a neighbour's halo reads -- were stored and drained before the
+// activations, the interior row chunks after the pass's halo had come in.  C2 2-7 % slower in fp64
 // and fp32 (profiles/r03l_edge_first_ab.log), and C3 / C4 3-8 % slower (round 4,
 // profiles/r04u_edge_first_throughput_ab.log): the drain before the activations is latency, not the
 // number of stores, and the extra per-visit barrier and edge-column stores cost more than it saves.
-#ifndef EIK_WB_LINE
-#define EIK_WB_LINE 0
-#endif
-#ifndef EIK_EDGE_FIRST
-#define EIK_EDGE_FIRST 0
-#endif
+// EIK_WB_LINE, round 6, likewise: whole 128-B lines stored whenever one of their chunks changed.)
 
 // EIK_ACT_SPLIT (persistent in-place passes, default on): the neighbour activations' state-word
 // atomics are issued at the pass boundary and their queueing is finished by wave 0 when its next
@@ -468,6 +465,9 @@ __device__ __forceinline__ void process_tile(const Fim2dArgs& a, int tile, TileL
     if (lane < 4) cell_c(Ts, (lane >> 1) * (kLds - 1) * kLds + (lane & 1) * (kLds - 1), (lane & 1) * (kLds - 1)) = INF;  // corners
     __syncthreads();
     EIK_PROBE(1);
+    // (the cap's load is awaited here, with the staging's: its first use is phase B of the
+    // write-back, where the wait would also cover the stores just issued)
+    if constexpr (CAP) asm volatile("" ::"v"(capv));
 
     // PERSISTENT mode revisits a tile that changed IN PLACE, up to a.max_passes times
     // (EIK_OPT_PASSES; by default 24 for one map, 2 for a batch): its interior is already in LDS
@@ -523,109 +523,132 @@ __device__ __forceinline__ void process_tile(const Fim2dArgs& a, int tile, TileL
         // PERSISTENT mode, a.sched bit 0: consume the activations that reached this busy tile
         // during the pass (neighbours' edges drained before their atomicOr, and this clear comes
         // before the halo reload) -- an in-place pass then serves them instead of a re-queued
-        // visit.  Issued now, awaited with the write-back's drain.
+        // visit.  Issued behind the thread's stores (below), awaited with the write-back's drain.
         unsigned pend_old = 0;
-        if (COH && (a.sched & 1) && tid == 0) pend_old = atomicAnd(&a.qstate[tile], kBusy | kVisited);
         // ---- write back changed cells, collect side flags (and entering values, ordered mode).
-        // EIK_EDGE_FIRST (persistent mode, full tiles): only the tile's edge cells -- the values a
-        // neighbour's halo reads -- are stored and drained before the activations; the interior
-        // row chunks (bit k of defer_rows: this thread's row chunk k) are stored after the pass's
-        // halo has come in and drain during the next sweep, or before the visit's finish (the
-        // persistent loop drains every wave before qfinish).  Nobody else reads a busy tile's
-        // interior: its next visit starts after that finish.
-        unsigned fl = 0;
-        unsigned defer_rows = 0;
-        R kmin_self = INF, kmin[4] = {INF, INF, INF, INF};
+        // Phase A, straight-line: the thread's 16 cells come out of LDS in one batch (one wait),
+        // the changed row chunks are stored at once, and nothing else stands before the last
+        // store -- the drain (1.4-2.9 us for a tile, tools/lat_probe.hip) starts as early as it
+        // can and runs under phase B.
+        R nv[16];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int ry = (tid >> 4) + 16 * k;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) nv[4 * k + e] = cell_t(Ts, (ry + 1) * kLds + cx + e + 1, cx + e + 1);
+        }
+        // chg, bit 4 k + e: the cell decreased by more than the tolerance and lies in the raster
+        // (a ghost cell inside a cut tile is lowered by the halo reload, never by a sweep)
+        unsigned chg = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int ry = (tid >> 4) + 16 * k;
             const int64_t gy = y0 + ry;
-            R nv[4];
             bool any = false;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                nv[e] = cell_t(Ts, (ry + 1) * kLds + cx + e + 1, cx + e + 1);
-                any |= nv[e] < told[4 * k + e];
-                // (a ghost cell inside a cut tile is lowered by the halo reload, never by a sweep)
-                if (nv[e] < told[4 * k + e] * keep && (full || (gy < a.H && x0 + cx + e < a.W))) {
-                    fl |= 128u;  // changed in this visit
-                    kmin_self = umin(kmin_self, nv[e]);
-                    // A neighbour can only improve if this edge value undercuts the neighbour's
-                    // adjacent cell (the halo value, stale => larger => conservative).
-                    // (a.tcap: an edge value above the map's cap activates nobody)
-                    const int lx = cx + e + 1, ly = ry + 1;
-                    const bool act = !CAP || nv[e] <= capv;
-                    if (act && ry == 0 && nv[e] < cell_t(Ts, lx, lx)) { fl |= 1u; kmin[0] = umin(kmin[0], nv[e]); }
-                    if (act && ry == kTile - 1 && nv[e] < cell_t(Ts, (kLds - 1) * kLds + lx, lx)) { fl |= 2u; kmin[1] = umin(kmin[1], nv[e]); }
-                    if (act && cx + e == 0 && nv[e] < cell_t(Ts, ly * kLds, 0)) { fl |= 4u; kmin[2] = umin(kmin[2], nv[e]); }
-                    if (act && cx + e == kTile - 1 && nv[e] < cell_t(Ts, ly * kLds + kLds - 1, kLds - 1)) { fl |= 8u; kmin[3] = umin(kmin[3], nv[e]); }
-                    const int64_t gx = x0 + cx + e;  // subdomain edges inside a partial tile (DD)
-                    if (gy == a.H - 1 && ry != kTile - 1) fl |= 32u;
-                    if (gx == a.W - 1 && cx + e != kTile - 1) fl |= 64u;
-                }
+                const int i = 4 * k + e;
+                any |= nv[i] < told[i];
+                const bool in = full || (gy < a.H && x0 + cx + e < a.W);
+                chg |= (nv[i] < told[i] * keep && in) ? 1u << i : 0u;
             }
-#if EIK_WB_LINE
-            // (A/B, round 6: store whole 128-B lines -- every chunk of a line whose any chunk changed)
-            if (full) {
-#pragma unroll
-                for (int m = 1; m < 128 / (4 * (int)sizeof(R)); m <<= 1) any |= __shfl_xor((int)any, m) != 0;
-            }
-#endif
             if (any) {
-                if (COH && EIK_EDGE_FIRST && full && ry != 0 && ry != kTile - 1) {
-                    if (cx == 0 && nv[0] < told[4 * k]) T.st(gy * a.W + x0, nv[0]);
-                    if (cx == kTile - 4 && nv[3] < told[4 * k + 3]) T.st(gy * a.W + x0 + kTile - 1, nv[3]);
-                    defer_rows |= 1u << k;
-                } else if (full) {
-                    T.st4(gy * a.W + x0 + cx, nv);
+                if (full) {
+                    const R v[4] = {nv[4 * k], nv[4 * k + 1], nv[4 * k + 2], nv[4 * k + 3]};
+                    T.st4(gy * a.W + x0 + cx, v);
                 } else {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         const int64_t gx = x0 + cx + e;
-                        if (gy < a.H && gx < a.W && nv[e] < told[4 * k + e]) T.st(gy * a.W + gx, nv[e]);
+                        if (gy < a.H && gx < a.W && nv[4 * k + e] < told[4 * k + e]) T.st(gy * a.W + gx, nv[4 * k + e]);
                     }
                 }
                 // the edge columns' copies (kEcol), drained with T's stores; a cut tile's cells past
                 // the raster are never read as a halo, so the copy may hold them too
-                if (kEcol<R> && cx == 0 && nv[0] < told[4 * k]) E.st(eidx(tile, 0, ry), nv[0]);
-                if (kEcol<R> && cx == kTile - 4 && nv[3] < told[4 * k + 3]) E.st(eidx(tile, 1, ry), nv[3]);
-            }
-            if (COH) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) told[4 * k + e] = nv[e];  // what memory holds now
+                if (kEcol<R> && cx == 0 && nv[4 * k] < told[4 * k]) E.st(eidx(tile, 0, ry), nv[4 * k]);
+                if (kEcol<R> && cx == kTile - 4 && nv[4 * k + 3] < told[4 * k + 3]) E.st(eidx(tile, 1, ry), nv[4 * k + 3]);
             }
         }
-        if (fl) atomicOr(&L.flags, fl);
-        if (a.delta < INF || a.bctl) {  // ordered list mode / priority bands: the entering keys
-            if (kmin_self < INF) atomicMin(&L.key[0], __float_as_uint((float)kmin_self));
+        // (the index's lane term is zero, but keeps the address a per-lane value: with a wave-uniform
+        // address the compiler's atomic optimizer broadcasts the result by v_readfirstlane right
+        // behind the atomic, and wave 0 would wait there for its stores' drain and the atomic's round
+        // trip before phase B -- as it did when the atomic was issued ahead of the write-back)
+        if (COH && (a.sched & 1) && tid == 0)
+            pend_old = atomicAnd(&a.qstate[tile + (int)__builtin_amdgcn_mbcnt_lo(0u, 0u)], kBusy | kVisited);
+        __builtin_amdgcn_sched_barrier(0);  // phase B's LDS reads stay behind the stores
+        if (COH) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q)
-                if (kmin[q] < INF) atomicMin(&L.key[q + 1], __float_as_uint((float)kmin[q]));
+            for (int i = 0; i < 16; ++i) told[i] = nv[i];  // what memory holds now
         }
-        if (tid == 0) L.last = a.max_rounds == 1 ? -1 : (int)last_changed;  // -1: see flags bit 7
-        if (COH && (a.sched & 1) && tid == 0) L.pend = pend_old;
-        if constexpr (COH) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains
-        __syncthreads();
-        EIK_PROBE(7);
-        // the deferred interior row chunks (told holds what they store)
-        auto store_deferred = [&]() {
-            asm volatile("" ::: "memory");  // not above the halo / activation round trips
+        // Phase B, LDS and registers only, while the stores drain: the flags and keys from chg.
+        // A neighbour can only improve if an edge value undercuts the neighbour's adjacent cell
+        // (the halo value, stale => larger => conservative); the four sides are four blocks chosen
+        // by tid alone, each reading its four halo cells in one batch.
+        // (a.tcap: an edge value above the map's cap activates nobody)
+        const bool keys = a.delta < INF || a.bctl;  // ordered list mode / priority bands: the entering keys
+        unsigned fl = chg ? 128u : 0u;              // changed in this visit
+        R kmin_self = INF, kmin[4] = {INF, INF, INF, INF};
+        if (keys) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (defer_rows & (1u << k)) {
-                    const R v[4] = {told[4 * k], told[4 * k + 1], told[4 * k + 2], told[4 * k + 3]};
-                    T.st4((y0 + (tid >> 4) + 16 * k) * a.W + x0 + cx, v);
-                }
+            for (int i = 0; i < 16; ++i) kmin_self = umin(kmin_self, (chg >> i) & 1u ? nv[i] : INF);
+        }
+        // cells i0 + di * j (j = 0..3) of the thread against the halo cells h0 + dh * j in column hc
+        auto edge = [&](int q, int i0, int di, int h0, int dh, int hc) {
+            R hv[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) hv[j] = cell_t(Ts, h0 + dh * j, hc < 0 ? cx + j + 1 : hc);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = i0 + di * j;
+                const bool act = !CAP || nv[i] <= capv;
+                const bool hit = ((chg >> i) & 1u) && act && nv[i] < hv[j];
+                fl |= hit ? 1u << q : 0u;
+                kmin[q] = umin(kmin[q], hit ? nv[i] : INF);
             }
         };
+        const int ly0 = (tid >> 4) + 1;  // LDS row of the thread's chunk 0
+        if ((tid >> 4) == 0) edge(0, 0, 1, cx + 1, 1, -1);                           // N: chunk 0 is row 0
+        if ((tid >> 4) == 15) edge(1, 12, 1, (kLds - 1) * kLds + cx + 1, 1, -1);     // S: chunk 3 is row 63
+        if ((tid & 15) == 0) edge(2, 0, 4, ly0 * kLds, 16 * kLds, 0);                // W: cell 0 of each chunk
+        if ((tid & 15) == 15) edge(3, 3, 4, ly0 * kLds + kLds - 1, 16 * kLds, kLds - 1);  // E: cell 3
+        if (!full) {  // subdomain edges inside a partial tile (DD)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int ry = (tid >> 4) + 16 * k;
+                if (y0 + ry == a.H - 1 && ry != kTile - 1 && ((chg >> (4 * k)) & 0xFu)) fl |= 32u;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+                if (x0 + cx + e == a.W - 1 && cx + e != kTile - 1 && (chg & (0x1111u << e))) fl |= 64u;
+        }
+        // the wave's flags and keys, reduced in registers; one lane per wave merges them in LDS
+        const unsigned wfl = wave_reduce_idem(fl, [](unsigned x, unsigned y) { return x | y; });
+        if (wfl && lane == 0) atomicOr(&L.flags, wfl);
+        if (keys) {
+            const R km[5] = {kmin_self, kmin[0], kmin[1], kmin[2], kmin[3]};
+#pragma unroll
+            for (int q = 0; q < 5; ++q) {
+                const unsigned wk = wave_reduce_idem(__float_as_uint((float)km[q]), [](unsigned x, unsigned y) { return min(x, y); });
+                if (wk < 0x7f800000u && lane == 0) atomicMin(&L.key[q], wk);
+            }
+        }
+        if (tid == 0) L.last = a.max_rounds == 1 ? -1 : (int)last_changed;  // -1: see flags bit 7
+        // every storing wave drains.  (The builtin first: the compiler's own wait bookkeeping does not
+        // see the asm's, would hold the state word's atomic for outstanding on the paths around its
+        // use, and would then wait for it -- and for the stores -- where the next pass reuses its
+        // register, ahead of phase B.  vmcnt(0), expcnt and lgkmcnt untouched: 0x0F70 on gfx9.)
+        if constexpr (COH) {
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        if (COH && (a.sched & 1) && tid == 0) L.pend = pend_old;
+        __syncthreads();
+        EIK_PROBE(7);
         if (COH) {
             const unsigned f = L.flags;  // uniform
             const unsigned pend = L.pend & (kPending | kFromN | kFromS | kFromW | kFromE);
             const bool self = (f & 128u) != 0u;
-            if ((!self && !pend) || pass + 1 >= a.max_passes || a.max_rounds != 1) {
-                store_deferred();  // drained by the persistent loop before the finish
-                break;
-            }
+            if ((!self && !pend) || pass + 1 >= a.max_passes || a.max_rounds != 1) break;
             // the halo reload is issued first and the budget charge goes to wave 1, so wave 0's
             // activation atomics are the only round trips the next pass waits for
             const R hv = load_halo();
@@ -641,7 +664,6 @@ __device__ __forceinline__ void process_tile(const Fim2dArgs& a, int tile, TileL
             if (defer && tid == 0) L.flags_acc |= f & 0x6fu;
             dirs = self ? 0xFu : sweep_dirs(pend);  // a self revisit: every direction
             cell_t(Ts, h, hcol) = hv;
-            store_deferred();  // after the halo value is in: they drain during the next sweep
             __syncthreads();  // every wave has read L.flags and its halo side is in
             if (tid == 0) {
                 L.flags = 0;  // next OR-ed after the next sweep barrier
@@ -808,8 +830,13 @@ __device__ __forceinline__ void live_agent(const Fim2dArgs& a, unsigned* sh) {
 // VGPRs -> 3 workgroups per CU; 4: <= 128 VGPRs -> 4 per CU, a few spills).  Large rasters
 // (maps of >= kWideTiles tiles: the throughput-bound regime) run the 4-wave form -- 16384^2 on one GPU
 // +10-15 %, 4096^2 -3 % (profiles/r02r_wps_ab.log).
+// The one-wave forms state what they reached on their own before the batched write-back, whose
+// nv[16] beside told[16] otherwise costs a workgroup per CU: fp32 3 (<= 168 VGPRs; 175 without),
+// fp64 2 (<= 256; the REF forms, at 280 / 282, 1).
+template <typename R, int WPS, bool REF>
+constexpr int kPersistWaves = WPS > 1 ? WPS : sizeof(R) == 4 ? 3 : REF ? 1 : 2;
 template <typename R, int WPS, bool CAP = false, bool REF = false>
-__global__ __launch_bounds__(kThreads, WPS) void fim2d_persist_kernel(Fim2dArgs a) {
+__global__ __launch_bounds__(kThreads, (kPersistWaves<R, WPS, REF>)) void fim2d_persist_kernel(Fim2dArgs a) {
     __shared__ TileLds<R> L;
     if (a.live && blockIdx.x == 0) {
         __shared__ unsigned sh[4];
@@ -822,10 +849,6 @@ __global__ __launch_bounds__(kThreads, WPS) void fim2d_persist_kernel(Fim2dArgs 
     int tile = -1;
     unsigned nvis = 0;  // wave 0 lane 0: visits not yet added to the global counter
     for (;;) {
-        if (EIK_EDGE_FIRST && tile >= 0) {  // uniform: every wave's deferred interior stores
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // complete before the finish
-            __syncthreads();
-        }
         // wave 0 retires the previous tile (lanes 0..4 activate, then lane 0 finishes) while
         // wave 1 takes the next one; waves 2 and 3 go straight to the barrier
         if (threadIdx.x < 64) {
