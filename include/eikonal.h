@@ -81,10 +81,12 @@ typedef enum {
     EIK_OPT_QTIMEOUT = 7,    /* persistent mode: seconds a workgroup may wait on the FIFO before
                                 the solve fails with EIK_ERR_HIP instead of hanging (default 30) */
     EIK_OPT_MAX_VISITS = 8,  /* persistent mode: tile visits after which a solve fails with
-                                EIK_ERR_NOCONVERGE (0: default 1024 x tiles + 2^20)            */
+                                EIK_ERR_NOCONVERGE (0: default 1024 x tiles + 2^20; 2D solves: x the
+                                raster's elongation, (tile columns + tile rows) / (2 sqrt(tiles)),
+                                where that exceeds 1)                                          */
     EIK_OPT_PASSES = 9,      /* persistent mode: sweep passes a visit may run in place while its
                                 tile keeps changing before it is re-queued (0, the default:
-                                24 for a single map, 16 for a single fp32 map of >= 16384
+                                40 for a single map, 16 for a single fp32 map of >= 16384
                                 tiles, 2 for a batch of maps)                                  */
     EIK_OPT_FRESH_FIRST = 10,/* persistent mode: 1 queues a tile's first activation ahead of
                                 re-visits while the queue has a backlog (default 0: one FIFO)  */
@@ -128,12 +130,19 @@ typedef enum {
                                 launch; eik_fim2d_solve then solves again with the FIFO.         */
     EIK_OPT_PRIO_DISPATCH = 18, /* band entries moved to the FIFO per dispatch, 1..128 (0, the
                                 default: 128 on maps of >= 16384 tiles, else 16)                */
-    EIK_OPT_EXACT_BAND = 19  /* biComputeTmap / rover path and fp64 FM3D early exits: 1 replays the
+    EIK_OPT_EXACT_BAND = 19, /* biComputeTmap / rover path and fp64 FM3D early exits: 1 replays the
                                 reference's sequential narrow band in pop order from the converged
                                 fields (csrc/bidir_exact.hip): its tentative band values, its LIFO
                                 order of equal T and so its nodeJoin / closed set, bit for bit; 0
                                 (default) = band cells at their final (2D: relaxed) values (GPU <=
                                 reference <= 1.03 x GPU), ties by node index / strict < T[start] */
+    EIK_OPT_WIDE = 20        /* fp32 2D persistent solves: which form of the kernel is launched
+                                (and the co-resident workgroup count that goes with it).  < 0
+                                (default) = by size: the 4-waves-per-SIMD form on maps of >= 16384
+                                tiles, else the narrow form; 0 = always the narrow form; 1 =
+                                always the 4-waves-per-SIMD form.  The pass cap, the bands and the
+                                dispatch batch keep their own defaults (EIK_OPT_PASSES, _PRIO,
+                                _PRIO_DISPATCH); fp64 solves ignore it.                          */
 } eik_option;
 
 typedef enum { EIK_MODE_LIST = 0, EIK_MODE_PERSISTENT = 1 } eik_mode;
@@ -184,6 +193,12 @@ int eik_fronts_info(const eik_ctx* ctx, int64_t out[10]);
  * passes, out[1..2] relaxation sweeps (goal, start front), out[3] tie-run launches, out[4] its
  * device time in microseconds; all 0 when it did not run. */
 int eik_exact_info(const eik_ctx* ctx, int64_t out[5]);
+
+/* What the last 2D solve started on the context (eik_fim2d_start and every entry point that goes
+ * through it; the internal coarse solve of the capped fronts and the cost builder's do not count)
+ * took: out[0] 1 = the 4-waves-per-SIMD fp32 form was launched, out[1] 1 = priority bands were set
+ * up, out[2] the pass cap, out[3] the bands' dispatch batch (0 without bands). */
+int eik_last_form(const eik_ctx* ctx, int64_t out[4]);
 
 /* B independent maps (goal sweep / terrain Monte-Carlo): cost, T: B*H*W; goals: B x (x, y). */
 int eik_tmap2d_batch_f32(eik_ctx* ctx, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,

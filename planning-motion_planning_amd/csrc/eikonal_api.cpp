@@ -154,6 +154,8 @@ struct eik_ctx {
     double prio = -1.0;
     int prio_ring = 0;           // EIK_OPT_PRIO_RING: slots per priority band (0: pow2 >= 2 x the tiles)
     int prio_dispatch = 0;       // EIK_OPT_PRIO_DISPATCH: band entries per dispatch (0: 128 on maps of >= kWideTiles, else 16)
+    int wide = -1;               // EIK_OPT_WIDE: the fp32 2D persistent kernel's form (< 0: by size, wide_form())
+    int64_t last_form[4] = {};   // eik_last_form: wide form launched, bands set up, pass cap, dispatch batch
     // EIK_OPT_LAYER_PLANAR (default 1): the layered solver works on layer-planar copies.  C5 kernel
     // traffic per launch 9.06 -> 3.92 GB (fp32), 20.3 -> 8.6 GB (fp64), the time within noise
     // (the layered sweep is VALU-bound; profiles/r05c_pmc_traffic_c5*.json, r05h_prio_planar_ab.log)
@@ -220,6 +222,7 @@ struct eik_fim2d {
     bool band_overflow = false;          // the last launch stopped on a full priority band (qerror bit 4)
     bool no_bands = false;               // ... so this solver's next starts use the FIFO
     int persist_grid = 0;                // co-resident workgroups of the persistent kernel
+    bool persist_wide = false;           // ... of which form (EIK_OPT_WIDE can change it between solves)
     // live domain decomposition: hold word on the device, mailbox of the halo agent on the host
     DevBuf hold;
     LiveBox* box = nullptr;              // pinned, coherent
@@ -228,6 +231,22 @@ struct eik_fim2d {
     int lnl = 0, lz0 = 0;
     int64_t lL = 1;
 };
+
+// The fp32 2D persistent kernel's form: the 4-waves-per-SIMD one on one large raster (a batch of
+// small maps: no gain), or as EIK_OPT_WIDE says.  fp64 has the one form.
+static bool wide_form(const eik_fim2d* f) {
+    if (f->f64) return false;
+    return f->ctx->wide >= 0 ? f->ctx->wide != 0 : f->a.tiles_per_map >= kWideTiles;
+}
+
+// ... and its co-resident workgroups, kept per solver and form
+static int persist_resident(eik_fim2d* f, bool wide) {
+    if (f->persist_grid == 0 || f->persist_wide != wide) {
+        f->persist_grid = fim2d_persist_resident(f->f64, f->ctx->cu_count, wide);
+        f->persist_wide = wide;
+    }
+    return f->persist_grid;
+}
 
 static int set_err(eik_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
@@ -408,6 +427,7 @@ int eik_set_option(eik_ctx* c, int opt, double v) {
         case EIK_OPT_LAYER_PLANAR: c->layer_planar = v != 0; break;
         case EIK_OPT_PATH_LOOP: c->path_loop = std::max(0, std::min(4, (int)v)); break;
         case EIK_OPT_EXACT_BAND: c->exact_band = v != 0; break;
+        case EIK_OPT_WIDE: c->wide = v < 0 ? -1 : v != 0 ? 1 : 0; break;
         case EIK_OPT_FRONTS_CAP: c->fronts_cap = v <= 0 ? 0.0 : v == 1 ? kFrontsMargin : std::max(1.0, v); break;
         default: return set_err(c, EIK_ERR_ARG, "unknown option %d", opt);
     }
@@ -605,7 +625,14 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
                       : batch                                             ? 2
                       : (!f->f64 && f->a.tiles_per_map >= kWideTiles)     ? 16
                                                                           : 40;
-    f->a.qbudget = c->max_visits ? c->max_visits : 1024ull * (unsigned long long)(f->B * f->a.tiles_per_map) + (1ull << 20);
+    // The default visit budget, 1024 per tile (in-place passes count), x the raster's elongation: a
+    // tile is re-visited as corrections travel down the chain of tiles behind it, and that chain is
+    // ntx + nty long -- 2 sqrt(tiles) on a square raster (factor 1), but the whole raster on a strip.
+    // Measured on valid 3-cell-wide U(1, 10) strips, visits + passes per tile: 1024 tiles 830 (fp32) /
+    // 980 (fp64), 16384 tiles 2350 / 1590 -- the flat 1024 per tile reported the latter as not converging.
+    const double elong = std::max(1.0, (f->a.ntx + f->a.nty) / (2.0 * std::sqrt((double)f->a.tiles_per_map)));
+    f->a.qbudget = c->max_visits ? c->max_visits
+                                 : (unsigned long long)(1024.0 * elong * (double)(f->B * f->a.tiles_per_map)) + (1ull << 20);
     f->iterations = 0;
     f->host_syncs = 0;
     f->sweep_ms = 0.0;
@@ -630,8 +657,10 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     // since the 128-entry dispatches (round 6: C4 at one GPU fp32 18.4 -> 19.5 Gcells/s mean of 5 same-box
     // alternations, 145 k -> 108 k visits, profiles/r06s7/r06s7_c4f32_prio_ab{,2}.log)
     const bool f32_wide = !f->f64 && f->B == 1 && f->a.tiles_per_map >= kWideTiles && !dd_block;
+    // (the tile count is fp32's gate, as include/eikonal.h states it: a thin raster of >= kWideTiles
+    // tiles can have fewer than 4096^2 cells, and took 16 passes and the wide form but no bands)
     const double prio = c->prio >= 0 ? c->prio
-                        : f32_wide ? default_prio(f->H, f->W, 4096.0)
+                        : f32_wide ? default_prio(f->H, f->W, 0.0)
                         : !f->f64  ? 0.0
                         : dd_block ? std::max(1.0, default_prio(f->H, f->W, 0.0))
                                    : default_prio(f->H, f->W, 4096.0);
@@ -647,6 +676,11 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
                                          : f->a.tiles_per_map >= kWideTiles ? 128u : 16u;  // (fim_engine.hpp band_dispatch)
     }
     HIPCHK(c, fim2d_init(f->a, f->f64, (int)f->B, (const int64_t*)f->goals.p, (unsigned*)f->edge.p, f->stream));
+    // eik_last_form (the launch fills in the kernel's form)
+    c->last_form[0] = 0;
+    c->last_form[1] = f->a.bctl != nullptr;
+    c->last_form[2] = f->a.max_passes;
+    c->last_form[3] = f->a.bctl ? (int64_t)f->a.disp : 0;
     f->started = true;
     f->need_rewind = false;  // the init cleared the queue words
     return EIK_OK;
@@ -791,9 +825,9 @@ int eik_fim2d_iterate(eik_fim2d* f, int64_t max_iters, int64_t* active) {
             }
             HIPCHK(c, hipEventRecord(f->ev_pool[f->ev_used++], f->stream));
         }
-        const bool wide = !f->f64 && f->a.tiles_per_map >= kWideTiles;  // one large raster (a batch of small maps: no gain)
-        if (f->persist_grid == 0) f->persist_grid = fim2d_persist_resident(f->f64, c->cu_count, wide);
-        const int g = std::min(grid, f->persist_grid);
+        const bool wide = wide_form(f);
+        const int g = std::min(grid, persist_resident(f, wide));
+        c->last_form[0] = wide;
         f->a.fresh_first = c->fresh_first;
         f->a.sched = c->sched;
         f->a.live_pack = c->live_pack;
@@ -1027,13 +1061,14 @@ int eik_fim2d_launch(eik_fim2d* f, int live) {
         return set_err(c, EIK_ERR_ARG, "eik_fim2d_launch needs the persistent mode (EIK_OPT_MODE)");
     HIPCHK(c, hipSetDevice(c->device));
     const int grid = c->grid > 0 ? c->grid : 4 * c->cu_count;
-    const bool wide = !f->f64 && f->a.tiles_per_map >= kWideTiles;  // one large raster (a batch of small maps: no gain)
+    const bool wide = !f->lnl && wide_form(f);
     if (f->lnl) {  // a layered block (eik_fim3dl_create): the layered kernel's co-resident count
         int& res = c->resident_l[f->f64 ? 1 : 0][f->lnl];
         if (res == 0) res = fim2dl_persist_resident(f->lnl, f->f64, c->cu_count);
         f->persist_grid = res;
-    } else if (f->persist_grid == 0) {
-        f->persist_grid = fim2d_persist_resident(f->f64, c->cu_count, wide);
+    } else {
+        (void)persist_resident(f, wide);
+        c->last_form[0] = wide;
     }
     Fim2dArgs a = f->a;
     if (live) {
@@ -1409,8 +1444,11 @@ static int solve_fronts(eik_ctx* c, eik_fim2d* f, double* dcost, double* dT, con
         }
         const int64_t gc[4] = {g[0] / F, g[1] / F, g[2] / F, g[3] / F};
         const eik_stats keep = c->last;  // the coarse estimate's solve is not the caller's
+        int64_t keep_form[4];
+        memcpy(keep_form, c->last_form, sizeof keep_form);
         int rc = eik_fim2d_solve(fc, ccost, cT, gc, st);
         c->last = keep;
+        memcpy(c->last_form, keep_form, sizeof keep_form);
         if (rc) return rc;
         HIPCHK(c, fronts_estimate(cT, cT + nc, nc, c->work.p, (double)F, c->fronts_cap, chk, st));
         f->a.tcap = chk->caps;
@@ -1446,6 +1484,12 @@ static int solve_fronts(eik_ctx* c, eik_fim2d* f, double* dcost, double* dT, con
 int eik_exact_info(const eik_ctx* c, int64_t out[5]) {
     if (!c || !out) return EIK_ERR_ARG;
     for (int i = 0; i < 5; ++i) out[i] = (int64_t)c->exact_info[i];
+    return EIK_OK;
+}
+
+int eik_last_form(const eik_ctx* c, int64_t out[4]) {
+    if (!c || !out) return EIK_ERR_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = c->last_form[i];
     return EIK_OK;
 }
 
@@ -2095,8 +2139,11 @@ static int cm_fill(eik_ctx* c, unsigned char* m, int64_t H, int64_t W, float* fc
     HIPCHK(c, cm_fill_cost(m, H * W, fcost, st));
     const int64_t goal[2] = {0, 0};
     const eik_stats keep = c->last;  // the builder's internal solves do not count as the caller's
+    int64_t keep_form[4];
+    memcpy(keep_form, c->last_form, sizeof keep_form);
     int rc = eik_fim2d_solve(f, fcost, fT, goal, st);
     c->last = keep;
+    memcpy(c->last_form, keep_form, sizeof keep_form);
     if (rc) return rc;
     HIPCHK(c, cm_fill_apply(m, fT, H * W, st));
 #else

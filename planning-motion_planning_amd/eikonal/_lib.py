@@ -15,7 +15,7 @@ PATH_DONE, PATH_FALLBACK, PATH_ERROR = 0, 1, 2
 OPT_MAX_ROUNDS, OPT_SYNC_EVERY, OPT_TIMING, OPT_GRID, OPT_TOL, OPT_DELTA = 0, 1, 2, 3, 4, 5
 OPT_MODE, OPT_QTIMEOUT, OPT_MAX_VISITS, OPT_PASSES, OPT_FRESH_FIRST, OPT_SCHED, OPT_PATH_LOOP = 6, 7, 8, 9, 10, 11, 12
 OPT_FRONTS_CAP, OPT_LIVE_PACK, OPT_PRIO, OPT_LAYER_PLANAR, OPT_PRIO_RING, OPT_PRIO_DISPATCH = 13, 14, 15, 16, 17, 18
-OPT_EXACT_BAND = 19
+OPT_EXACT_BAND, OPT_WIDE = 19, 20
 MODE_LIST, MODE_PERSISTENT = 0, 1
 
 i64 = C.c_int64
@@ -131,6 +131,7 @@ def lib():
         L.eik_bidir_join_f64.argtypes = [vp, _f64p, _f64p, i64, i64, _f64p, _f64p, _u32p, _i64p]
         L.eik_fronts_info.argtypes = [vp, _i64p]
         L.eik_exact_info.argtypes = [vp, _i64p]
+        L.eik_last_form.argtypes = [vp, _i64p]
         L.eik_tmap2d_batch_f32.argtypes = [vp, _f32p, i64, i64, i64, _i64p, _f32p]
         L.eik_path2d_f64.argtypes = [vp, _f64p, i64, i64, _f64p, _f64p, C.c_double, _f64p, i64, P(i64), P(C.c_int)]
         L.eik_gradient2d_f64.argtypes = [vp, _f64p, i64, i64, _f64p, _f64p]
@@ -207,7 +208,7 @@ EXPORTED = [
     "eik_node_shm_close", "eik_node_shm_unlink", "eik_ipc_alloc", "eik_ipc_free", "eik_ipc_open", "eik_ipc_close",
     "eik_rover_assemble", "eik_rover_path_f64", "eik_arm_obst_map_f64", "eik_arm_tunnel_cost_f64",
     "eik_arm_path_f64", "eik_tmap3d_batch_f64", "eik_host_alloc", "eik_host_free", "eik_fim2d_qcount",
-    "eik_fim3dl_create", "eik_fim3dl_start",
+    "eik_fim3dl_create", "eik_fim3dl_start", "eik_last_form",
 ]
 
 
@@ -363,6 +364,13 @@ class Context:
         self._chk(lib().eik_exact_info(self._h, out))
         return {"passes": int(out[0]), "sweeps": out[1:3].tolist(), "tie_launches": int(out[3]),
                 "ms": out[4] / 1000.0}
+
+    def last_form(self):
+        """What the last 2D solve started on this context took (eik_last_form): the fp32 kernel's
+        4-waves-per-SIMD form, priority bands, the pass cap and the bands' dispatch batch."""
+        out = np.zeros(4, np.int64)
+        self._chk(lib().eik_last_form(self._h, out))
+        return {"wide": int(out[0]), "bands": int(out[1]), "passes": int(out[2]), "dispatch": int(out[3])}
 
     def path2d(self, T, init, end, tau=0.5):
         T = np.ascontiguousarray(T, dtype=np.float64)

@@ -17,7 +17,9 @@ pytestmark = pytest.mark.gpu
 OPP = {0: 1, 1: 0, 2: 3, 3: 2}
 
 
-def solve_blocks(cost, goal, px, py, f64, mode, exchange_every=4):
+def solve_blocks(cost, goal, px, py, f64, mode, exchange_every=4, options=None, forms=None):
+    """options: further Context options; forms: a list that receives the context's last_form()
+    after every block's launch of the first round."""
     import eikonal
     from eikonal import _lib as L
     from eikonal import dd
@@ -25,7 +27,7 @@ def solve_blocks(cost, goal, px, py, f64, mode, exchange_every=4):
     dev = torch.device("cuda", 0)
     H, W = cost.shape
     R = px * py
-    ctx = eikonal.Context(0)
+    ctx = eikonal.Context(0, options=options)
     ctx.set_option(L.OPT_MODE, mode)
     dt = torch.float64 if f64 else torch.float32
     blocks = [dd.Block(H, W, px, py, r) for r in range(R)]
@@ -42,6 +44,8 @@ def solve_blocks(cost, goal, px, py, f64, mode, exchange_every=4):
     for rounds in range(1, 100000):
         for loc, send in zip(locs, sends):
             loc.iterate(exchange_every)
+            if forms is not None and rounds == 1:
+                forms.append(ctx.last_form())
             loc.pack_edges(*send)
         for r, b in enumerate(blocks):
             for s in range(4):
@@ -69,12 +73,8 @@ def oracle_field(cost, goal):
         O.set_strict(True)
 
 
-@pytest.mark.parametrize("mode", ["persistent", "list"])
-@pytest.mark.parametrize("px,py", [(2, 1), (1, 2), (2, 2), (4, 2)])
-@pytest.mark.parametrize("f64", [True, False])
-def test_dd_blocks_match_single_domain(mode, px, py, f64):
-    from eikonal import _lib as L
-
+def dd_case(px, py, f64):
+    """test_dd_blocks_match_single_domain's raster and goal for a px x py split."""
     rng = np.random.default_rng(px * 10 + py)
     H, W = 390, 455  # blocks not multiples of the 64-cell tile
     cost = rng.uniform(1, 6, (H, W))
@@ -83,6 +83,16 @@ def test_dd_blocks_match_single_domain(mode, px, py, f64):
     cost[goal[1], goal[0]] = 1.0
     if not f64:
         cost = cost.astype(np.float32).astype(np.float64)
+    return cost, goal
+
+
+@pytest.mark.parametrize("mode", ["persistent", "list"])
+@pytest.mark.parametrize("px,py", [(2, 1), (1, 2), (2, 2), (4, 2)])
+@pytest.mark.parametrize("f64", [True, False])
+def test_dd_blocks_match_single_domain(mode, px, py, f64):
+    from eikonal import _lib as L
+
+    cost, goal = dd_case(px, py, f64)
     T, rounds = solve_blocks(cost, goal, px, py, f64, L.MODE_PERSISTENT if mode == "persistent" else L.MODE_LIST)
     R = oracle_field(cost, goal)
     fin = np.isfinite(R)

@@ -95,6 +95,16 @@ def test_c1_config(ctx, golden, name, f64):
     ((2048, 2048), "blobs", 7),
 ])
 def test_vs_oracle(ctx, shape, kind, seed):
+    c, goal = vs_oracle_case(shape, kind, seed)
+    H, W = shape
+    R = oracle_field(c, goal)
+    check_field(ctx.tmap2d(c, goal, dtype=np.float32), R, goal, False)
+    if H * W <= 1 << 20:
+        check_field(ctx.tmap2d(c, goal, dtype=np.float64), R, goal, True)
+
+
+def vs_oracle_case(shape, kind, seed):
+    """test_vs_oracle's raster and goal (also run on the wide fp32 form: tests/test_gpu_wide.py)."""
     rng = np.random.default_rng(seed)
     H, W = shape
     c = rng.uniform(1, 10, shape)
@@ -113,10 +123,7 @@ def test_vs_oracle(ctx, shape, kind, seed):
     c = c.astype(np.float32).astype(np.float64)
     goal = [W // 3, H // 2] if W > 1 else [0, H // 2]
     c[goal[1], goal[0]] = 1.0
-    R = oracle_field(c, goal)
-    check_field(ctx.tmap2d(c, goal, dtype=np.float32), R, goal, False)
-    if H * W <= 1 << 20:
-        check_field(ctx.tmap2d(c, goal, dtype=np.float64), R, goal, True)
+    return c, goal
 
 
 def test_enclosed_goal_and_unreachable(ctx):
@@ -242,9 +249,9 @@ def test_fresh_visits_read_no_T(ctx, shape, f64):
 @pytest.mark.parametrize("passes", [1, 2, 8, 16])
 def test_pass_cap_option(passes):
     """EIK_OPT_PASSES (in-place passes per persistent visit) changes the schedule, not the field:
-    a single map and a batch against the oracle at caps other than the defaults (24 for a single
-    map -- 16 for one of >= 16384 tiles --, 2 for a batch; 2 is also run here on the single map and
-    1 / 16 on the batch)."""
+    a single map and a batch against the oracle at caps other than the defaults (40 for a single
+    map -- 16 for one fp32 map of >= 16384 tiles --, 2 for a batch; 2 is also run here on the single
+    map and 1 / 16 on the batch)."""
     import eikonal
     from eikonal import _lib as L
 
@@ -269,6 +276,16 @@ def test_pass_cap_option(passes):
         c.close()
 
 
+def schedule_raster(rng):
+    """test_schedule_options' single map: 640 x 770 (ragged both ways), 15 % obstacles."""
+    cost = rng.uniform(1, 10, (640, 770))
+    cost[rng.random(cost.shape) < 0.15] = np.inf
+    cost = cost.astype(np.float32).astype(np.float64)
+    goal = [500, 120]
+    cost[goal[1], goal[0]] = 1.0
+    return cost, goal
+
+
 @pytest.mark.parametrize("opts", [(("SCHED", 0),), (("SCHED", 2),), (("SCHED", 3),), (("FRESH_FIRST", 1),),
                                   (("SCHED", 0), ("FRESH_FIRST", 1)), (("PRIO", 0.1),), (("PRIO", 1),),
                                   (("PRIO", 1e4),), (("PRIO", 1), ("SCHED", 0)),
@@ -285,11 +302,7 @@ def test_schedule_options(opts):
         for name, v in opts:
             c.set_option(getattr(L, "OPT_" + name), v)
         rng = np.random.default_rng(12)
-        cost = rng.uniform(1, 10, (640, 770))
-        cost[rng.random(cost.shape) < 0.15] = np.inf
-        cost = cost.astype(np.float32).astype(np.float64)
-        goal = [500, 120]
-        cost[goal[1], goal[0]] = 1.0
+        cost, goal = schedule_raster(rng)
         check_field(c.tmap2d(cost, goal, dtype=np.float32), oracle_field(cost, goal), goal, False)
         costs = rng.uniform(1, 8, (3, 130, 260)).astype(np.float32)
         goals = np.array([[3, 4], [250, 120], [128, 64]], np.int64)
@@ -300,6 +313,18 @@ def test_schedule_options(opts):
             check_field(T[b], oracle_field(costs[b], goals[b]), goals[b], False)
     finally:
         c.close()
+
+
+def visit_budget_raster(neg):
+    """test_visit_budget_device_buffers' fp32 raster (neg: with a negative-cost block) and goal."""
+    rng = np.random.default_rng(3)
+    cost = rng.uniform(1, 10, (1024, 1024)).astype(np.float32)
+    cost[rng.random(cost.shape) < 0.15] = np.inf
+    if neg:
+        cost[400:600, 400:600] = -2.0
+    goal = np.array([[512, 300]], np.int64)
+    cost[300, 512] = 1.0
+    return cost, goal
 
 
 @pytest.mark.parametrize("neg", [False, True])
@@ -313,13 +338,7 @@ def test_visit_budget_device_buffers(neg):
     import eikonal
     from eikonal import _lib as L
 
-    rng = np.random.default_rng(3)
-    cost = rng.uniform(1, 10, (1024, 1024)).astype(np.float32)
-    cost[rng.random(cost.shape) < 0.15] = np.inf
-    if neg:
-        cost[400:600, 400:600] = -2.0
-    goal = np.array([[512, 300]], np.int64)
-    cost[300, 512] = 1.0
+    cost, goal = visit_budget_raster(neg)
     c = eikonal.Context(0)
     try:
         c.set_option(L.OPT_MAX_VISITS, 128)

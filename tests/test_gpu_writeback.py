@@ -180,6 +180,11 @@ def test_dd_block_with_ghosts(mode, f64):
     it packs are its last row / column.  (The per-side "edge changed" word the write-back's bits 32 /
     64 feed has no reader in the C ABI or the Python API, so it is exercised here -- the ghosts bind
     it -- but not read; tests/test_gpu_dd_live.py covers its effect at larger size.)"""
+    dd_block_with_ghosts(mode, f64)
+
+
+def dd_block_with_ghosts(mode, f64, options=None):
+    """test_dd_block_with_ghosts' body; options: further Context options -> the context's last_form()."""
     import eikonal
     import torch
     from eikonal import _lib as L
@@ -191,7 +196,7 @@ def test_dd_block_with_ghosts(mode, f64):
     R = oracle_field(("cut", (H, W), goal), cost, goal)
     dev = torch.device("cuda", 0)
     dt = torch.float64 if f64 else torch.float32
-    ctx = eikonal.Context(0)
+    ctx = eikonal.Context(0, options=options)
     try:
         ctx.set_option(L.OPT_MODE, L.MODE_PERSISTENT if mode == "persistent" else L.MODE_LIST)
         ctx.set_option(L.OPT_QTIMEOUT, 5.0)
@@ -212,9 +217,11 @@ def test_dd_block_with_ghosts(mode, f64):
         torch.cuda.synchronize()
         Tg = T.cpu().numpy()
         edges = [s.cpu().numpy() for s in send]
+        form = ctx.last_form()
         fim.close()
     finally:
         ctx.close()
     check_field(Tg, R, goal, f64)
     for got, want in zip(edges, (Tg[0, :], Tg[-1, :], Tg[:, 0], Tg[:, -1])):
         assert np.array_equal(got, want)
+    return form
