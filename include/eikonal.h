@@ -338,6 +338,46 @@ int eik_path2d_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t H, int64_t 
                    const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
                    void* stream);
 
+/* ---- batched paths: P getPathGDM walks in one launch (no reference counterpart) -----------
+ * d_T holds B fields of one shape ([B][H][W], dtype); path p walks field map_of[p] from
+ * inits[p] to ends[p] (P x 2 rows of (x, y)) into d_out + p * cap * 2, d_n_out[p], d_status[p]
+ * (an eik_path_status per path: one path that errors or falls back does not fail the call).  Every
+ * path is bit-identical to eik_path2d_dev on its field with the same tau and cap.
+ * map_of, inits, ends are HOST arrays of P entries, read before the call returns and put on the
+ * device in stream order (calls issued back to back on one stream need no synchronisation between
+ * them); map_of == NULL: path p walks field p when P == B, field 0 when B == 1.
+ * EIK_ERR_ARG (checked on the host, nothing launched): a map_of entry outside [0, B), map_of NULL
+ * with P != B and B > 1, P < 1, cap < 2, H or W < 3, tau <= 0, a NULL pointer.
+ * One workgroup per path on its own CU: P above the CU count runs in rounds.  Async on `stream`. */
+int eik_path2d_batch_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
+                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
+                         int64_t cap, int64_t* d_n_out, int* d_status, void* stream);
+
+/* The same on host buffers (synchronous): T: B*H*W fp64, uploaded once; out: P x cap x 2, of which
+ * path p's first n_out[p] rows are written (the rest is left as it was); n_out, status: P. */
+int eik_path2d_batch_f64(eik_ctx* ctx, const double* T, int64_t B, int64_t H, int64_t W, int64_t P,
+                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
+                         int64_t cap, int64_t* n_out, int* status);
+
+/* FastMarching3D.getPathGDM, batched as above: d_T [B][H][W][L]; inits, ends: P x 3 (x, y, z);
+ * d_out: P x cap x 3.  Every path is bit-identical to eik_path3d_dev.  EIK_ERR_ARG as above, with
+ * H, W or L < 1 for the shape. */
+int eik_path3d_batch_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t L,
+                         int64_t P, const int32_t* map_of, const double* inits, const double* ends, double tau,
+                         double* d_out, int64_t cap, int64_t* d_n_out, int* d_status, void* stream);
+int eik_path3d_batch_f64(eik_ctx* ctx, const double* T, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
+                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
+                         int64_t cap, int64_t* n_out, int* status);
+
+/* End to end on B maps (terrain Monte-Carlo, goal sweep): eik_tmap2d_batch_f32's solve, the fields
+ * kept on the device, then one batched walk from starts[b] (B x 2 doubles) to goals[b] (B x 2,
+ * (x, y)) on fp32 field b.  paths: B x cap x 2, n_out, status: B (per map; a start outside map b is
+ * that path's EIK_PATH_ERROR).  Only the paths come back, and the B*H*W fields too when T_out is
+ * not NULL.  Synchronous. */
+int eik_plan2d_batch_f32(eik_ctx* ctx, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,
+                         const double* starts, double tau, double* paths, int64_t cap, int64_t* n_out, int* status,
+                         float* T_out);
+
 /* 3D solve on device buffers (synchronous: returns after convergence; stats via
  * eik_get_stats). */
 int eik_fim3d_solve(eik_ctx* ctx, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,

@@ -8,6 +8,9 @@ the gradient and the path extraction run on the GPU (libeikonal.so via ctypes):
   getPathGDM(T, init, end, tau)          FastMarching.py:164-236  -> GPU path kernel
   computeGradient(cost, point=[])        FastMarching.py:242-300  -> GPU gradient kernel
 
+An addition with no reference counterpart:
+  getPathsGDM(T, inits, end, tau)        many getPathGDM walks on one field in one GPU launch
+
 Scalar/list helpers that the reference exposes at module level keep their reference
 semantics on the host (they operate on Python scalars and lists the caller owns):
   getEikonal :17-29, getNeighbours :31-42, updateNode :44-80, getMinNB :82-89,
@@ -163,6 +166,20 @@ def getPathGDM(totalCostMap, initWaypoint, endWaypoint, tau):
     if status == PATH_ERROR:
         raise IndexError("getPathGDM: the descent left the field (the reference raises here too)")
     return path
+
+
+def getPathsGDM(totalCostMap, initWaypoints, endWaypoint, tau):
+    """No reference counterpart: getPathGDM from every row of initWaypoints (P, 2) to endWaypoint on
+    one field, in one launch -> a list of P (K, 2) float64 paths, each equal to getPathGDM's for
+    that start; IndexError if any of them raises there."""
+    inits = np.asarray(initWaypoints, dtype=np.float64)
+    inits = inits.reshape(-1, inits.shape[-1])[:, :2]
+    end = np.asarray(endWaypoint, dtype=np.float64).reshape(-1)[:2]
+    res = _ctx().path2d_batch(np.ascontiguousarray(totalCostMap, dtype=np.float64), inits, end, float(tau))
+    bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
+    if bad:
+        raise IndexError(f"getPathsGDM: the descent of path {bad[0]} left the field (getPathGDM raises here too)")
+    return [path for path, _ in res]
 
 
 def computeGradient(cost, point=[]):

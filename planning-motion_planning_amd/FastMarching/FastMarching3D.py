@@ -2,6 +2,7 @@
 
   computeTmap(costMap, goal, start)   FastMarching3D.py:126-145 -> GPU 3D block-FIM + early exit
   getPathGDM(T, init, end, tau)       FastMarching3D.py:198-271 -> GPU path kernel
+  getPathsGDM(T, inits, end, tau)     no reference counterpart: many getPathGDM walks in one launch
 Host-side scalar/list helpers keep their reference semantics: updateNode :19-101,
 sumlist :103-107, getMinNB :109-123, interpolatePoint :275-314.
 
@@ -141,3 +142,17 @@ def getPathGDM(totalCostMap, initWaypoint, endWaypoint, tau):
     if status == PATH_ERROR:
         raise IndexError("getPathGDM (3D): the descent left the volume (the reference raises here too)")
     return path
+
+
+def getPathsGDM(totalCostMap, initWaypoints, endWaypoint, tau):
+    """No reference counterpart: getPathGDM from every row of initWaypoints (P, 3) to endWaypoint on
+    one volume, in one launch -> a list of P (K, 3) float64 paths, each equal to getPathGDM's for
+    that start; IndexError if any of them raises there."""
+    inits = np.asarray(initWaypoints, dtype=np.float64)
+    inits = inits.reshape(-1, inits.shape[-1])[:, :3]
+    end = np.asarray(endWaypoint, np.float64).reshape(-1)[:3]
+    res = _ctx().path3d_batch(np.ascontiguousarray(totalCostMap, dtype=np.float64), inits, end, float(tau))
+    bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
+    if bad:
+        raise IndexError(f"getPathsGDM (3D): the descent of path {bad[0]} left the volume (getPathGDM raises here too)")
+    return [path for path, _ in res]

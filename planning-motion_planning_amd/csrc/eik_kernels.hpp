@@ -195,6 +195,29 @@ struct Gdm3dArgs {
 };
 hipError_t gdm3d(const Gdm3dArgs& a, bool f64, hipStream_t st);
 
+// Batched path extraction (gdm.hip: gdm2d_kernel / gdm3d_kernel on GdmBatchArgs): P walks in one
+// launch, workgroup p = path p.  One descriptor per path; everything else is the batch's.
+struct GdmDesc {
+    int32_t map;           // which of the B fields the path walks
+    int32_t pad;
+    double init[3], end[3];  // (x, y(, z)); 2D reads [0..1]
+};
+struct GdmBatchArgs {
+    const void* T;         // [B][H][W]([L]) fields (R), device
+    int64_t H, W, L;       // L: 3D only
+    int64_t P;             // paths = workgroups
+    const GdmDesc* desc;   // [P], device
+    double tau;
+    long steps;
+    double* out;           // [P][cap][2 or 3]
+    int64_t cap;
+    int64_t* n_out;        // [P]
+    int* status;           // [P]
+    int fused;             // 2D: EIK_OPT_PATH_LOOP
+};
+hipError_t gdm2d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st);
+hipError_t gdm3d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st);
+
 // Cost-raster builder (costmap.hip), f64 DEM -> f64 cost, uint8 obstacle masks.
 hipError_t cm_normals(const double* Z, int64_t H, int64_t W, double size, unsigned long long* zmin, double slope_max,
                       unsigned char* obst, double* Nx, double* Ny, double* Nz, hipStream_t st);

@@ -121,6 +121,16 @@ class CopyPool {
     bool quit_ = false;
 };
 
+// Descriptors of one batched path call (eik_path*_batch_dev): a pinned host block and its device
+// twin.  The call fills h, copies it to d on the caller's stream, launches, and records ev; the
+// block is free again once ev has completed (stage_desc).
+struct DescBlock {
+    GdmDesc* h = nullptr;
+    GdmDesc* d = nullptr;
+    int64_t cap = 0;
+    hipEvent_t ev = nullptr;
+};
+
 }  // namespace
 
 constexpr double kFrontsMargin = 1.25;  // capped bidirectional fronts (solve_fronts)
@@ -195,6 +205,8 @@ struct eik_ctx {
     CopyPool* pool = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t e3[2] = {nullptr, nullptr};
+    std::vector<DescBlock> desc;       // batched paths: descriptor blocks in flight or free (stage_desc)
+    size_t desc_next = 0;
 };
 
 struct eik_fim2d {
@@ -392,6 +404,14 @@ void eik_destroy(eik_ctx* c) {
     for (int b = 0; b < 2; ++b) {
         if (c->stage[b]) (void)hipHostFree(c->stage[b]);
         if (c->stage_ev[b]) (void)hipEventDestroy(c->stage_ev[b]);
+    }
+    for (DescBlock& b : c->desc) {
+        if (b.ev) {
+            (void)hipEventSynchronize(b.ev);
+            (void)hipEventDestroy(b.ev);
+        }
+        if (b.h) (void)hipHostFree(b.h);
+        if (b.d) (void)hipFree(b.d);
     }
     c->pool = nullptr;  // (the process-wide pool stays)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
@@ -1630,6 +1650,202 @@ int eik_path2d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, const doub
     return EIK_OK;
 }
 
+// ---- batched paths: P walks in one launch (gdm.hip: gdm2d_kernel / gdm3d_kernel on GdmBatchArgs)
+constexpr size_t kDescBlocks = 8;  // descriptor blocks kept per context
+
+// A descriptor block of >= P entries that no earlier call still uses: a block whose event has
+// completed (grown if too small), else a new one, else -- kDescBlocks calls in flight -- the oldest,
+// after waiting for it.
+static int stage_desc(eik_ctx* c, int64_t P, DescBlock** out) {
+    DescBlock* b = nullptr;
+    for (DescBlock& k : c->desc)
+        if (hipEventQuery(k.ev) == hipSuccess && (!b || (b->cap < P && k.cap >= P))) b = &k;
+    if (!b && c->desc.size() < kDescBlocks) {
+        c->desc.emplace_back();
+        b = &c->desc.back();
+        HIPCHK(c, hipEventCreateWithFlags(&b->ev, hipEventDisableTiming));
+    }
+    if (!b) {
+        b = &c->desc[c->desc_next++ % c->desc.size()];
+        HIPCHK(c, hipEventSynchronize(b->ev));
+    }
+    if (b->cap < P) {
+        if (b->h) (void)hipHostFree(b->h);
+        if (b->d) (void)hipFree(b->d);
+        b->h = b->d = nullptr;
+        b->cap = 0;
+        const int64_t cap = std::max<int64_t>(256, P);
+        HIPCHK(c, hipHostMalloc((void**)&b->h, sizeof(GdmDesc) * cap));
+        HIPCHK(c, hipMalloc((void**)&b->d, sizeof(GdmDesc) * cap));
+        b->cap = cap;
+    }
+    *out = b;
+    return EIK_OK;
+}
+
+// Host-side checks (batch_check) and staging (batch_stage) shared by the 2D and 3D batch entries
+// (dim = 2 or 3): on EIK_OK a.desc holds the P descriptors, on the device in stream order, and *blk
+// is to be marked busy (hipEventRecord on st) after the launch.  Nothing is launched on an error.
+static int batch_check(eik_ctx* c, int dim, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
+                       const int32_t* map_of, const double* inits, const double* ends, double tau, int64_t cap) {
+    if (!inits || !ends) return set_err(c, EIK_ERR_ARG, "batched path: NULL argument");
+    if (B < 1) return set_err(c, EIK_ERR_ARG, "batched path: B = %ld fields (>= 1 needed)", (long)B);
+    if (P < 1 || P > 0x7fffffff) return set_err(c, EIK_ERR_ARG, "batched path: P = %ld paths (1 .. 2^31 - 1)", (long)P);
+    if (cap < 2) return set_err(c, EIK_ERR_ARG, "batched path: cap = %ld rows per path (>= 2 needed)", (long)cap);
+    if (!(tau > 0)) return set_err(c, EIK_ERR_ARG, "batched path: tau = %g (> 0 needed)", tau);
+    if (dim == 2 ? (H < 3 || W < 3) : (H < 1 || W < 1 || L < 1))
+        return set_err(c, EIK_ERR_ARG, "batched path: field of %ld x %ld x %ld too small", (long)H, (long)W, (long)L);
+    if (!map_of && P != B && B != 1)
+        return set_err(c, EIK_ERR_ARG, "batched path: map_of is NULL with P = %ld paths on B = %ld fields (P == B or B == 1)",
+                       (long)P, (long)B);
+    if (map_of)
+        for (int64_t p = 0; p < P; ++p)
+            if (map_of[p] < 0 || map_of[p] >= B)
+                return set_err(c, EIK_ERR_ARG, "batched path: map_of[%ld] = %d outside [0, %ld)", (long)p, map_of[p], (long)B);
+    return EIK_OK;
+}
+static int batch_stage(eik_ctx* c, int dim, const void* d_T, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
+                       const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
+                       int64_t cap, int64_t* d_n_out, int* d_status, hipStream_t st, GdmBatchArgs& a, DescBlock** blk) {
+    if (!c) return EIK_ERR_ARG;
+    if (!d_T || !d_out || !d_n_out || !d_status) return set_err(c, EIK_ERR_ARG, "batched path: NULL argument");
+    int rc = batch_check(c, dim, B, H, W, L, P, map_of, inits, ends, tau, cap);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    rc = stage_desc(c, P, blk);
+    if (rc) return rc;
+    GdmDesc* h = (*blk)->h;
+    for (int64_t p = 0; p < P; ++p) {
+        h[p].map = map_of ? map_of[p] : B == 1 ? 0 : (int32_t)p;
+        h[p].pad = 0;
+        for (int k = 0; k < 3; ++k) {
+            h[p].init[k] = k < dim ? inits[dim * p + k] : 0.0;
+            h[p].end[k] = k < dim ? ends[dim * p + k] : 0.0;
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync((*blk)->d, h, sizeof(GdmDesc) * P, hipMemcpyHostToDevice, st));
+    a.T = d_T;
+    a.H = H;
+    a.W = W;
+    a.L = L;
+    a.P = P;
+    a.desc = (*blk)->d;
+    a.tau = tau;
+    a.steps = (long)std::nearbyint(15000.0 / tau);  // as the single entries
+    a.out = d_out;
+    a.cap = cap;
+    a.n_out = d_n_out;
+    a.status = d_status;
+    a.fused = c->path_loop;
+    return EIK_OK;
+}
+
+// The synchronous host entries' tail: path p's n_out[p] rows into out + p * cap * dim (rows past
+// them stay as the caller left them), after the walks on c->stream.
+static int batch_fetch(eik_ctx* c, int dim, int64_t P, int64_t cap, const double* d_out, const int64_t* d_n,
+                       const int* d_st, double* out, int64_t* n_out, int* status) {
+    HIPCHK(c, hipMemcpyAsync(n_out, d_n, sizeof(int64_t) * P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(status, d_st, sizeof(int) * P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int64_t p = 0; p < P; ++p) {
+        if (n_out[p] > cap) n_out[p] = cap;
+        if (n_out[p] > 0)
+            HIPCHK(c, hipMemcpyAsync(out + p * cap * dim, d_out + p * cap * dim, sizeof(double) * dim * n_out[p],
+                                     hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
+// the host entries' device results in c->work: out [P][cap][dim] | n_out [P] | status [P]
+static int batch_work(eik_ctx* c, int dim, int64_t P, int64_t cap, double** d_out, int64_t** d_n, int** d_st) {
+    HIPCHK(c, c->work.ensure(sizeof(double) * dim * cap * P + (sizeof(int64_t) + sizeof(int)) * P + 64));
+    *d_out = (double*)c->work.p;
+    *d_n = (int64_t*)(*d_out + dim * cap * P);
+    *d_st = (int*)(*d_n + P);
+    return EIK_OK;
+}
+
+int eik_path2d_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
+                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
+                         int64_t cap, int64_t* d_n_out, int* d_status, void* stream) {
+    GdmBatchArgs a{};
+    DescBlock* blk = nullptr;
+    int rc = batch_stage(c, 2, d_T, B, H, W, 1, P, map_of, inits, ends, tau, d_out, cap, d_n_out, d_status,
+                         (hipStream_t)stream, a, &blk);
+    if (rc) return rc;
+    HIPCHK(c, gdm2d_batch(a, dtype == EIK_F64, (hipStream_t)stream));
+    HIPCHK(c, hipEventRecord(blk->ev, (hipStream_t)stream));
+    return EIK_OK;
+}
+
+int eik_path2d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int64_t W, int64_t P, const int32_t* map_of,
+                         const double* inits, const double* ends, double tau, double* out, int64_t cap, int64_t* n_out,
+                         int* status) {
+    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched path: NULL argument") : EIK_ERR_ARG;
+    int rc = batch_check(c, 2, B, H, W, 1, P, map_of, inits, ends, tau, cap);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = B * H * W;
+    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
+    double* d_out;
+    int64_t* d_n;
+    int* d_st;
+    rc = batch_work(c, 2, P, cap, &d_out, &d_n, &d_st);
+    if (rc) return rc;
+    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));  // the B fields, once
+    rc = eik_path2d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau, d_out, cap, d_n, d_st,
+                              c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
+        return rc;
+    }
+    return batch_fetch(c, 2, P, cap, d_out, d_n, d_st, out, n_out, status);
+}
+
+int eik_plan2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,
+                         const double* starts, double tau, double* paths, int64_t cap, int64_t* n_out, int* status,
+                         float* T_out) {
+    if (!c || !cost || !goals || !starts || !paths || !n_out || !status)
+        return c ? set_err(c, EIK_ERR_ARG, "batched plan: NULL argument") : EIK_ERR_ARG;
+    if (B < 1 || H < 3 || W < 3 || cap < 2 || !(tau > 0))
+        return set_err(c, EIK_ERR_ARG, "batched plan: B = %ld, field %ld x %ld, cap = %ld, tau = %g", (long)B, (long)H,
+                       (long)W, (long)cap, tau);
+    for (int64_t b = 0; b < B; ++b)
+        if (goals[2 * b] < 0 || goals[2 * b + 1] < 0 || goals[2 * b] >= W || goals[2 * b + 1] >= H)
+            return set_err(c, EIK_ERR_ARG, "goal (%ld, %ld) of map %ld outside %ldx%ld", (long)goals[2 * b],
+                           (long)goals[2 * b + 1], (long)b, (long)H, (long)W);
+    const int64_t n = B * H * W;
+    HIPCHK(c, hipSetDevice(c->device));
+    eik_fim2d* f = nullptr;
+    int rc = get_solver(c, B, H, W, EIK_F32, &f);
+    if (rc) return rc;
+    HIPCHK(c, c->cost.ensure(sizeof(float) * n));
+    HIPCHK(c, c->T.ensure(sizeof(float) * n));
+    double* d_out;
+    int64_t* d_n;
+    int* d_st;
+    rc = batch_work(c, 2, B, cap, &d_out, &d_n, &d_st);
+    if (rc) return rc;
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(float) * n, c->stream));
+    rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (rc) return rc;
+    rc = eik_fim2d_solve(f, c->cost.p, c->T.p, goals, c->stream);  // the B fields stay on the device
+    if (rc) return rc;
+    std::vector<double> ends(2 * B);
+    for (int64_t k = 0; k < 2 * B; ++k) ends[k] = (double)goals[k];
+    rc = eik_path2d_batch_dev(c, c->T.p, EIK_F32, B, H, W, B, nullptr, starts, ends.data(), tau, d_out, cap, d_n, d_st,
+                              c->stream);
+    if (rc) return rc;
+    rc = batch_fetch(c, 2, B, cap, d_out, d_n, d_st, paths, n_out, status);
+    if (rc) return rc;
+    if (T_out) {
+        HIPCHK(c, dev_to_host(c, T_out, c->T.p, sizeof(float) * n, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return EIK_OK;
+}
+
 // ------------------------------------------------------------------------------ 3D
 // Few-layer fp32 volumes (the rover's (x, y, mode) costmaps) on the layered 2D-tile solver:
 // layers z0 .. z0+nl-1 of a [H][W][L] volume, one persistent launch.
@@ -2100,6 +2316,43 @@ int eik_path3d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, int64_t L,
     *n_out = nn;
     *status = st;
     return EIK_OK;
+}
+
+int eik_path3d_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
+                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
+                         int64_t cap, int64_t* d_n_out, int* d_status, void* stream) {
+    GdmBatchArgs a{};
+    DescBlock* blk = nullptr;
+    int rc = batch_stage(c, 3, d_T, B, H, W, L, P, map_of, inits, ends, tau, d_out, cap, d_n_out, d_status,
+                         (hipStream_t)stream, a, &blk);
+    if (rc) return rc;
+    HIPCHK(c, gdm3d_batch(a, dtype == EIK_F64, (hipStream_t)stream));
+    HIPCHK(c, hipEventRecord(blk->ev, (hipStream_t)stream));
+    return EIK_OK;
+}
+
+int eik_path3d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
+                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
+                         int64_t cap, int64_t* n_out, int* status) {
+    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched 3D path: NULL argument") : EIK_ERR_ARG;
+    int rc = batch_check(c, 3, B, H, W, L, P, map_of, inits, ends, tau, cap);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = B * H * W * L;
+    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
+    double* d_out;
+    int64_t* d_n;
+    int* d_st;
+    rc = batch_work(c, 3, P, cap, &d_out, &d_n, &d_st);
+    if (rc) return rc;
+    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));  // the B volumes, once
+    rc = eik_path3d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, L, P, map_of, inits, ends, tau, d_out, cap, d_n, d_st,
+                              c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
+        return rc;
+    }
+    return batch_fetch(c, 3, P, cap, d_out, d_n, d_st, out, n_out, status);
 }
 
 int eik_gradient2d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, double* gnx, double* gny) {

@@ -308,8 +308,41 @@ __device__ void path_builder(PathLds& s, const R* __restrict__ T, int64_t H, int
     }
 }
 
-template <typename R, int LOOP>
-__global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(Gdm2dArgs a) {
+// One path's walk by one workgroup.  ONE kernel template for the single-path launch (A = Gdm2dArgs,
+// one workgroup) and the grid form (A = GdmBatchArgs: workgroup p takes descriptor p -- its map,
+// init, end --, walks its own map T + map * H * W and writes its own slab out + p * cap * 2, n_out[p],
+// status[p]): path_args turns either into the walk's Gdm2dArgs and everything below is shared, so
+// a batch walk is the single walk's arithmetic by construction.  Nothing below reads blockIdx or
+// a global word other than its own `a`'s: workgroups are independent.  The 128 KiB of windows take a
+// whole CU's LDS, so one workgroup runs per CU and those past the co-resident ones start as CUs
+// free up.
+template <typename R>
+__device__ __forceinline__ Gdm2dArgs path_args(const Gdm2dArgs& a) { return a; }
+template <typename R>
+__device__ __forceinline__ Gdm2dArgs path_args(const GdmBatchArgs& b) {
+    const int64_t p = blockIdx.x;
+    const GdmDesc* __restrict__ d = b.desc + p;
+    Gdm2dArgs a;
+    a.T = static_cast<const R*>(b.T) + (int64_t)d->map * b.H * b.W;
+    a.H = b.H;
+    a.W = b.W;
+    a.ix = d->init[0];
+    a.iy = d->init[1];
+    a.ex = d->end[0];
+    a.ey = d->end[1];
+    a.tau = b.tau;
+    a.steps = b.steps;
+    a.out = b.out + p * b.cap * 2;
+    a.cap = b.cap;
+    a.n_out = b.n_out + p;
+    a.status = b.status + p;
+    a.fused = b.fused;
+    return a;
+}
+
+template <typename R, int LOOP, typename A = Gdm2dArgs>
+__global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
+    const Gdm2dArgs a = path_args<R>(arg);
     __shared__ PathLds s;
     const R* __restrict__ T = static_cast<const R*>(a.T);
     const int64_t H = a.H, W = a.W;
@@ -778,6 +811,24 @@ hipError_t gdm2d(const Gdm2dArgs& a, bool f64, hipStream_t st) {
     return hipGetLastError();
 }
 
+hipError_t gdm2d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st) {
+    const dim3 g((unsigned)a.P), b(kPathThreads);
+    if (f64) {
+        if (a.fused == 4)      hipLaunchKernelGGL((gdm2d_kernel<double, 4, GdmBatchArgs>), g, b, 0, st, a);
+        else if (a.fused == 3) hipLaunchKernelGGL((gdm2d_kernel<double, 3, GdmBatchArgs>), g, b, 0, st, a);
+        else if (a.fused == 2) hipLaunchKernelGGL((gdm2d_kernel<double, 2, GdmBatchArgs>), g, b, 0, st, a);
+        else if (a.fused == 1) hipLaunchKernelGGL((gdm2d_kernel<double, 1, GdmBatchArgs>), g, b, 0, st, a);
+        else                   hipLaunchKernelGGL((gdm2d_kernel<double, 0, GdmBatchArgs>), g, b, 0, st, a);
+    } else {
+        if (a.fused == 4)      hipLaunchKernelGGL((gdm2d_kernel<float, 4, GdmBatchArgs>), g, b, 0, st, a);
+        else if (a.fused == 3) hipLaunchKernelGGL((gdm2d_kernel<float, 3, GdmBatchArgs>), g, b, 0, st, a);
+        else if (a.fused == 2) hipLaunchKernelGGL((gdm2d_kernel<float, 2, GdmBatchArgs>), g, b, 0, st, a);
+        else if (a.fused == 1) hipLaunchKernelGGL((gdm2d_kernel<float, 1, GdmBatchArgs>), g, b, 0, st, a);
+        else                   hipLaunchKernelGGL((gdm2d_kernel<float, 0, GdmBatchArgs>), g, b, 0, st, a);
+    }
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------- 3D path (FM3D)
 // np.gradient(T) along `axis` (0 y, 1 x, 2 z) at (j, i, k): central differences / 2 inside,
 // one-sided at the ends (numpy's edge_order=1), no inf awareness (FastMarching3D.py:200).
@@ -852,7 +903,7 @@ __device__ void build3(Path3Lds& s, const R* __restrict__ T, int64_t H, int64_t 
 }
 
 template <typename R>
-__device__ void path3_builder(Path3Lds& s, const R* __restrict__ T, int64_t H, int64_t W, int64_t L) {
+__device__ __forceinline__ void path3_builder(Path3Lds& s, const R* __restrict__ T, int64_t H, int64_t W, int64_t L) {
     const int w = (int)(threadIdx.x >> 6) - 1;
     int seen = 0;
     unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
@@ -950,8 +1001,35 @@ __device__ __forceinline__ int64_t win_origin(int64_t lo, int64_t hi, int n, int
     return o < 0 ? 0 : o;
 }
 
+// as the 2D kernel: one template for the single launch (A = Gdm3dArgs) and the grid form (A =
+// GdmBatchArgs: workgroup p walks path p of volume desc[p].map into out + p * cap * 3)
 template <typename R>
-__global__ __launch_bounds__(kP3Threads) void gdm3d_kernel(Gdm3dArgs a) {
+__device__ __forceinline__ Gdm3dArgs path3_args(const Gdm3dArgs& a) { return a; }
+template <typename R>
+__device__ __forceinline__ Gdm3dArgs path3_args(const GdmBatchArgs& b) {
+    const int64_t p = blockIdx.x;
+    const GdmDesc* __restrict__ d = b.desc + p;
+    Gdm3dArgs a;
+    a.T = static_cast<const R*>(b.T) + (int64_t)d->map * b.H * b.W * b.L;
+    a.H = b.H;
+    a.W = b.W;
+    a.L = b.L;
+    for (int i = 0; i < 3; ++i) {
+        a.init[i] = d->init[i];
+        a.end[i] = d->end[i];
+    }
+    a.tau = b.tau;
+    a.steps = b.steps;
+    a.out = b.out + p * b.cap * 3;
+    a.cap = b.cap;
+    a.n_out = b.n_out + p;
+    a.status = b.status + p;
+    return a;
+}
+
+template <typename R, typename A = Gdm3dArgs>
+__global__ __launch_bounds__(kP3Threads) void gdm3d_kernel(A arg) {
+    const Gdm3dArgs a = path3_args<R>(arg);
     __shared__ Path3Lds sl;
     if (threadIdx.x == 0) {
         sl.req_seq = 0;
@@ -1438,6 +1516,14 @@ hipError_t gdm3d(const Gdm3dArgs& a, bool f64, hipStream_t st) {
         hipLaunchKernelGGL(gdm3d_kernel<double>, dim3(1), dim3(kP3Threads), 0, st, a);
     else
         hipLaunchKernelGGL(gdm3d_kernel<float>, dim3(1), dim3(kP3Threads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t gdm3d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st) {
+    if (f64)
+        hipLaunchKernelGGL((gdm3d_kernel<double, GdmBatchArgs>), dim3((unsigned)a.P), dim3(kP3Threads), 0, st, a);
+    else
+        hipLaunchKernelGGL((gdm3d_kernel<float, GdmBatchArgs>), dim3((unsigned)a.P), dim3(kP3Threads), 0, st, a);
     return hipGetLastError();
 }
 

@@ -23,6 +23,7 @@ vp = C.c_void_p
 _f32p = np.ctypeslib.ndpointer(dtype=np.float32, flags="C_CONTIGUOUS")
 _f64p = np.ctypeslib.ndpointer(dtype=np.float64, flags="C_CONTIGUOUS")
 _i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
+_i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
 _u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
 _u8p = np.ctypeslib.ndpointer(dtype=np.uint8, flags="C_CONTIGUOUS")
 
@@ -191,6 +192,17 @@ def lib():
         L.eik_fim3dl_create.argtypes = [vp, i64, i64, i64, C.c_int, C.c_int, C.c_int, P(vp)]
         L.eik_fim3dl_start.argtypes = [vp, vp, vp, _i64p, vp]
         L.eik_fim2d_qcount.argtypes = [vp, P(C.c_uint64)]
+        # batched paths: map_of is a nullable int32 host array (passed as an address or None)
+        L.eik_path2d_batch_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, i64, vp, _f64p, _f64p, C.c_double, vp, i64,
+                                           vp, vp, vp]
+        L.eik_path2d_batch_f64.argtypes = [vp, _f64p, i64, i64, i64, i64, vp, _f64p, _f64p, C.c_double, _f64p, i64,
+                                           _i64p, _i32p]
+        L.eik_path3d_batch_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, i64, i64, vp, _f64p, _f64p, C.c_double, vp,
+                                           i64, vp, vp, vp]
+        L.eik_path3d_batch_f64.argtypes = [vp, _f64p, i64, i64, i64, i64, i64, vp, _f64p, _f64p, C.c_double, _f64p,
+                                           i64, _i64p, _i32p]
+        L.eik_plan2d_batch_f32.argtypes = [vp, _f32p, i64, i64, i64, _i64p, _f64p, C.c_double, _f64p, i64, _i64p,
+                                           _i32p, vp]
         _lib = L
         return L
 
@@ -209,6 +221,8 @@ EXPORTED = [
     "eik_rover_assemble", "eik_rover_path_f64", "eik_arm_obst_map_f64", "eik_arm_tunnel_cost_f64",
     "eik_arm_path_f64", "eik_tmap3d_batch_f64", "eik_host_alloc", "eik_host_free", "eik_fim2d_qcount",
     "eik_fim3dl_create", "eik_fim3dl_start", "eik_last_form",
+    "eik_path2d_batch_dev", "eik_path2d_batch_f64", "eik_path3d_batch_dev", "eik_path3d_batch_f64",
+    "eik_plan2d_batch_f32",
 ]
 
 
@@ -410,6 +424,67 @@ class Context:
                                        np.asarray(end, np.float64)[:3].copy(), float(tau), out, cap, C.byref(n),
                                        C.byref(st)))
         return out[: n.value].copy(), st.value
+
+    # -- batched paths (no reference counterpart): P walks in one launch, each bit-identical to the
+    # single call on its field
+    def _path_batch(self, dim, T, inits, ends, tau, map_of, cap):
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        if T.ndim == dim:
+            T = T[None]
+        if T.ndim != dim + 1:
+            raise ValueError(f"T must be a field of {dim} dimensions or a stack of them")
+        inits = np.ascontiguousarray(np.asarray(inits, np.float64).reshape(-1, np.shape(inits)[-1])[:, :dim])
+        P = len(inits)
+        ends = np.asarray(ends, np.float64)
+        ends = ends.reshape(-1, ends.shape[-1])[:, :dim]
+        if len(ends) == 1:
+            ends = np.repeat(ends, P, axis=0)
+        if len(ends) != P:
+            raise ValueError(f"{len(ends)} ends for {P} inits (one, or one per path)")
+        ends = np.ascontiguousarray(ends)
+        m = None if map_of is None else np.ascontiguousarray(map_of, np.int32).reshape(-1)
+        if m is not None and len(m) != P:
+            raise ValueError(f"{len(m)} map_of entries for {P} paths")
+        cap = int(round(15000 / tau)) + 4 if cap is None else int(cap)
+        out = np.empty((max(P, 1), max(cap, 1), dim))
+        n, st = np.zeros(max(P, 1), np.int64), np.zeros(max(P, 1), np.int32)
+        mp = None if m is None else m.ctypes.data
+        if dim == 2:
+            self._chk(lib().eik_path2d_batch_f64(self._h, T, T.shape[0], T.shape[1], T.shape[2], P, mp, inits, ends,
+                                                 float(tau), out, cap, n, st))
+        else:
+            self._chk(lib().eik_path3d_batch_f64(self._h, T, T.shape[0], T.shape[1], T.shape[2], T.shape[3], P, mp,
+                                                 inits, ends, float(tau), out, cap, n, st))
+        return [(out[p, : n[p]].copy(), int(st[p])) for p in range(P)]
+
+    def path2d_batch(self, T, inits, ends, tau=0.5, map_of=None, cap=None):
+        """P getPathGDM walks in one launch: T an H x W field or a stack B x H x W, inits P x 2, ends
+        one node or P of them, map_of the field of each path (None: path p on field p when P == B,
+        all on field 0 when B == 1) -> [(path (K, 2), status)] as P path2d calls would return."""
+        return self._path_batch(2, T, inits, ends, tau, map_of, cap)
+
+    def path3d_batch(self, T, inits, ends, tau=0.5, map_of=None, cap=None):
+        """path2d_batch for volumes (H x W x L or B x H x W x L, nodes (x, y, z)): as P path3d calls."""
+        return self._path_batch(3, T, inits, ends, tau, map_of, cap)
+
+    def plan2d_batch(self, costs, goals, starts, tau=0.5, want_fields=False):
+        """B fp32 maps end to end: the batched solve towards goals[b], the fields kept on the device,
+        then one batched walk from starts[b] -> [(path, status)] per map (and the B x H x W fields
+        with want_fields).  Equal to tmap2d_batch followed by a path per fp32 field."""
+        costs = np.ascontiguousarray(costs, dtype=np.float32)
+        B, H, W = costs.shape
+        g = np.ascontiguousarray(goals, np.int64).reshape(-1)
+        s = np.ascontiguousarray(np.asarray(starts, np.float64).reshape(B, -1)[:, :2])
+        if len(g) != 2 * B:
+            raise ValueError(f"{len(g) // 2} goals for {B} maps")
+        cap = int(round(15000 / tau)) + 4
+        out = np.empty((B, cap, 2))
+        n, st = np.zeros(B, np.int64), np.zeros(B, np.int32)
+        T = np.empty_like(costs) if want_fields else None
+        self._chk(lib().eik_plan2d_batch_f32(self._h, costs, B, H, W, g, s, float(tau), out, cap, n, st,
+                                             T.ctypes.data if want_fields else None))
+        res = [(out[b, : n[b]].copy(), int(st[b])) for b in range(B)]
+        return (res, T) if want_fields else res
 
     def costmap(self, Z, resolution, size, params=None):
         """Coupled_motion_planner.py:1101-1216 on the GPU: (cost [y][x] = the reference's cMap.T,
