@@ -935,12 +935,13 @@ __global__ void fim2d_seed_kernel(Fim2dArgs a, const int64_t* __restrict__ goals
         static_cast<R*>(a.ecol)[((int64_t)tile * 2 + (gx % kTile == 0 ? 0 : 1)) * kTile + gy % kTile] = R(0);
     if (a.mode == kModePersistent) {
         qpush(a, tile, kSelf | kVisited);  // visited: its T is not all +inf (kFreshSkip)
-        return;
+    } else {
+        a.mark[tile] = 1;  // enqueued for iteration 0
+        a.key[tile] = 0u;  // T = 0 enters at the goal
+        const int pos = atomicAdd(&a.counts[0], 1);
+        a.lists[pos] = tile;
     }
-    a.mark[tile] = 1;  // enqueued for iteration 0
-    a.key[tile] = 0u;  // T = 0 enters at the goal
-    const int pos = atomicAdd(&a.counts[0], 1);
-    a.lists[pos] = tile;
+    activate_goal_sides(a, tile, (int)(gy % kTile), (int)(gx % kTile), kTile);
 }
 
 // Priority bands (EIK_OPT_PRIO): the band width, 64 x the geometric mean of the finite positive costs

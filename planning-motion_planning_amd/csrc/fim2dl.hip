@@ -677,7 +677,9 @@ template <typename R>
 __global__ void fim2dl_seed_kernel(Fim2dArgs a, int64_t gx, int64_t gy, int64_t gz, int th) {
     static_cast<R*>(a.T)[(gy * a.W + gx) * a.ls + a.z0 + gz * a.lzs] = R(0);  // gz: the solved layer's index
     __threadfence();
-    qpush(a, (int)(gy / th) * a.ntx + (int)(gx / kTile), kSelf | kVisited);  // T not all +inf
+    const int tile = (int)(gy / th) * a.ntx + (int)(gx / kTile);
+    qpush(a, tile, kSelf | kVisited);  // T not all +inf
+    activate_goal_sides(a, tile, (int)(gy % th), (int)(gx % kTile), th);
 }
 
 

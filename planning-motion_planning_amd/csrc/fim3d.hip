@@ -285,26 +285,40 @@ __global__ void fim3d_init_kernel(R* __restrict__ T, int64_t n, unsigned* __rest
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < ntiles; i += stride) mark[i] = 0;
 }
 
+// The tiles a goal activates: its own and, where the goal lies on a face of its tile, the neighbour
+// across that face.  A visit flags a face only for the cells it lowered (process_tile3) and the goal is
+// never lowered, so T = 0 crosses a face only through an in-tile neighbour of the goal -- and when the
+// goal has none (a cut tile one cell wide, or every in-tile neighbour blocked) nothing would carry it
+// across: the neighbour's own visit, queued here, reads the goal as its halo.
+template <typename F>
+__device__ __forceinline__ void for_goal_tiles(const Fim3dArgs& a, int b, int64_t gx, int64_t gy, int64_t gz, F&& f) {
+    const int cx = (int)(gx % a.tx), cy = (int)(gy % a.ty), cz = (int)(gz % a.tz);
+    const int tile = b * a.tpv + ((int)(gy / a.ty) * a.ntx + (int)(gx / a.tx)) * a.ntz + (int)(gz / a.tz);
+    f(tile);
+    const bool on[6] = {cx == 0, cx == a.tx - 1, cy == 0, cy == a.ty - 1, cz == 0, cz == a.tz - 1};
+    for (int k = 0; k < 6; ++k) {
+        const int nb = on[k] ? face_neighbour3(a, tile, k) : -1;
+        if (nb >= 0) f(nb);
+    }
+}
+
+// T[goal of volume b] = 0 and its tiles on list 0 (the host zeroes the counts; the marks, zeroed by the
+// init kernel, keep a tile to one entry)
 template <typename R>
 __global__ void fim3d_seed_kernel(Fim3dArgs a, const int64_t* __restrict__ goals, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b == 0) {
-        a.counts[1] = 0;
-        a.counts[2] = 0;
-        a.counts[0] = B;
-    }
     if (b >= B) return;
     const int64_t gx = goals[3 * b], gy = goals[3 * b + 1], gz = goals[3 * b + 2];
     static_cast<R*>(a.T)[(int64_t)b * a.H * a.W * a.L + (gy * a.W + gx) * a.L + gz] = R(0);
-    const int tile = b * a.tpv + ((int)(gy / a.ty) * a.ntx + (int)(gx / a.tx)) * a.ntz + (int)(gz / a.tz);
-    a.mark[tile] = 1;
-    a.lists[b] = tile;
+    for_goal_tiles(a, b, gx, gy, gz, [&](int tile) { enqueue3(a, tile, 0, 1u); });
 }
 
 hipError_t fim3d_init(const Fim3dArgs& a, bool f64, const int64_t* d_goals, int B, hipStream_t st) {
     const int64_t n = (int64_t)B * a.H * a.W * a.L;
     const int grid = (int)std::min<int64_t>(4096, (n + 255) / 256);
     const int sg = (B + 255) / 256;
+    const hipError_t e = hipMemsetAsync(a.counts, 0, 3 * sizeof(int), st);
+    if (e != hipSuccess) return e;
     if (f64) {
         hipLaunchKernelGGL(fim3d_init_kernel<double>, dim3(grid), dim3(256), 0, st, static_cast<double*>(a.T), n,
                            a.mark, (int64_t)a.capacity);
@@ -335,7 +349,7 @@ __global__ void fim3d_pinit_kernel(R* __restrict__ T, int64_t n, unsigned* __res
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nslots; i += stride) qslot[i] = 0;
 }
 
-// T[goal of volume b] = 0 and its tile queued
+// T[goal of volume b] = 0 and its tiles queued (for_goal_tiles)
 template <typename R>
 __global__ void fim3d_pseed_kernel(Fim3dArgs a, Fim2dArgs q, const int64_t* __restrict__ goals, int B) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -343,7 +357,7 @@ __global__ void fim3d_pseed_kernel(Fim3dArgs a, Fim2dArgs q, const int64_t* __re
     const int64_t gx = goals[3 * b], gy = goals[3 * b + 1], gz = goals[3 * b + 2];
     static_cast<R*>(a.T)[(int64_t)b * a.H * a.W * a.L + (gy * a.W + gx) * a.L + gz] = R(0);
     __threadfence();
-    qpush(q, b * a.tpv + ((int)(gy / a.ty) * a.ntx + (int)(gx / a.tx)) * a.ntz + (int)(gz / a.tz), kSelf);
+    for_goal_tiles(a, b, gx, gy, gz, [&](int tile) { qpush(q, tile, kSelf); });
 }
 
 hipError_t fim3d_persist_init(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, const int64_t* d_goals, int B,

@@ -408,6 +408,20 @@ __device__ __forceinline__ void activate(const Fim2dArgs& a, int tile, int list,
         enqueue(a, tile, list, stamp, key);
 }
 
+// Seeding: the goal at row ry, column cx of `tile` (th rows) also activates the neighbour across every
+// tile side it lies on (list 0, stamp 1: the seed's).  A write-back flags a side only for the cells the
+// visit lowered and the goal is never lowered, so T = 0 crosses a side only through an in-tile
+// neighbour of the goal -- and where the goal has none (a cut tile one cell wide, or every in-tile
+// neighbour blocked) nothing would carry it across: the neighbour's own visit reads the goal as its halo.
+__device__ __forceinline__ void activate_goal_sides(const Fim2dArgs& a, int tile, int ry, int cx, int th) {
+    const int rem = tile % a.tiles_per_map;
+    const int ty = rem / a.ntx, tx = rem - ty * a.ntx;
+    if (ry == 0 && ty > 0) activate(a, tile - a.ntx, 0, 1u, 0.f, kFromS);
+    if (ry == th - 1 && ty + 1 < a.nty) activate(a, tile + a.ntx, 0, 1u, 0.f, kFromN);
+    if (cx == 0 && tx > 0) activate(a, tile - 1, 0, 1u, 0.f, kFromE);
+    if (cx == kTile - 1 && tx + 1 < a.ntx) activate(a, tile + 1, 0, 1u, 0.f, kFromW);
+}
+
 // Neighbour activations of a write-back with flags f: thread q in 1..4 handles one side (their
 // atomics overlap); thread 0 flags changed subdomain edges for the halo exchange.  (`tid`: the
 // caller's index for this role -- a lane of any one wave may serve, fim2d.hip's follow-through.)
