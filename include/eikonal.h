@@ -284,6 +284,51 @@ int eik_fim2d_active(eik_fim2d* fim, int64_t* active);
 /* statistics of the current/last solve (synchronises the stream to read the visit counter) */
 int eik_fim2d_stats(eik_fim2d* fim, eik_stats* out);
 
+/* Incremental re-solve after local cost changes (replanning; no reference counterpart, DESIGN.md
+ * §3.12).  The solver holds a converged field: its last solve ended with 0 active tiles, or the field
+ * was bound with eik_fim2d_adopt.  The caller has written the new costs into the bound cost buffer on
+ * the same stream and names K rectangles (x0, y0, x1, y1), half-open, clipped to the raster, that hold
+ * every changed cell, each with a kind:
+ *   EIK_CHANGE_ANY      a cost in the rectangle may have gone up (always safe to say)
+ *   EIK_CHANGE_LOWERED  the caller guarantees that no cost in the rectangle went up
+ * Only the cells whose old value depended on a cell of an ANY rectangle are reset and solved again;
+ * the rest of T is kept.  The result is the fixed point of the new cost -- exact for EIK_OPT_TOL = 0
+ * (the default); with a tolerance the kept cells carry the old solve's tolerance.
+ *
+ * One map (B = 1), no ghost strips, not a layered block, persistent mode (EIK_OPT_MODE, and a raster
+ * within its 32-bit offsets), either dtype, FIFO or priority bands.  Anything else -- a solver never
+ * started or adopted, a last solve that did not converge, a rectangle with x1 <= x0 or y1 <= y0 or
+ * wholly outside the raster, a kind other than 0 / 1, K > 1024 -- is EIK_ERR_ARG with a message, and
+ * nothing is launched.
+ *
+ * eik_fim2d_update   asynchronous: invalidates and queues the restart; eik_fim2d_iterate then converges
+ *                    it.  kinds == NULL: all ANY.  K == 0: a no-op, the solver stays converged.  The
+ *                    descriptors are staged through a pinned block: rects / kinds may be reused at once.
+ * eik_fim2d_resolve  update + iterate to convergence (synchronous); a full priority-band ring falls back
+ *                    to a full FIFO solve, as in eik_fim2d_solve.
+ *                    If the invalidation itself fails (its tile-visit budget, EIK_OPT_MAX_VISITS, or a queue
+ *                    wait past EIK_OPT_QTIMEOUT), the following iterate / this resolve returns that error
+ *                    and the bound T is INVALID: it may hold sign-marked (negative) values and a partly
+ *                    reset cone.  The same holds after any other error of the re-solve.  Solve from
+ *                    scratch (eik_fim2d_solve) before the field or a further update is used.
+ * eik_fim2d_adopt    binds d_cost / d_T where d_T is, by the caller's word, the converged field of some
+ *                    earlier cost of this raster for `goals`; nothing is solved.
+ * eik_fim2d_update_info  of the last update: out[0] cells invalidated, [1] tiles holding them, [2] tile
+ *                    visits of the invalidation flood, [3] tiles queued for the solve, [4] device time
+ *                    of the invalidation in microseconds, [5] 1 when eik_fim2d_resolve fell back to a
+ *                    full solve, else 0 (synchronises the stream). */
+typedef enum { EIK_CHANGE_ANY = 0, EIK_CHANGE_LOWERED = 1 } eik_change;
+int eik_fim2d_update(eik_fim2d* fim, const int64_t* rects, const int* kinds, int64_t K, void* stream);
+int eik_fim2d_resolve(eik_fim2d* fim, const int64_t* rects, const int* kinds, int64_t K, void* stream);
+int eik_fim2d_adopt(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* goals, void* stream);
+int eik_fim2d_update_info(eik_fim2d* fim, int64_t out[6]);
+/* Host buffers: cost_new and the converged field T of the earlier cost go up, T comes back as the
+ * field of cost_new (adopt + resolve on the context's cached solver). */
+int eik_tmap2d_update_f32(eik_ctx* ctx, const float* cost_new, float* T_inout, int64_t H, int64_t W, int64_t gx,
+                          int64_t gy, const int64_t* rects, const int* kinds, int64_t K);
+int eik_tmap2d_update_f64(eik_ctx* ctx, const double* cost_new, double* T_inout, int64_t H, int64_t W, int64_t gx,
+                          int64_t gy, const int64_t* rects, const int* kinds, int64_t K);
+
 /* Live domain decomposition (no reference counterpart: the multi-GPU split of SURVEY.md §8(e)).
  * eik_fim2d_launch(fim, 1) starts ONE persistent launch on the bound stream and returns at once.
  * Its last workgroup is a halo agent serving a pinned host mailbox while the others solve; the

@@ -8,8 +8,9 @@ the gradient and the path extraction run on the GPU (libeikonal.so via ctypes):
   getPathGDM(T, init, end, tau)          FastMarching.py:164-236  -> GPU path kernel
   computeGradient(cost, point=[])        FastMarching.py:242-300  -> GPU gradient kernel
 
-An addition with no reference counterpart:
+Additions with no reference counterpart:
   getPathsGDM(T, inits, end, tau)        many getPathGDM walks on one field in one GPU launch
+  updateTmap(costMap, Tmap, goal, changed)  computeTmap's field after local cost changes, from the old field
 
 Scalar/list helpers that the reference exposes at module level keep their reference
 semantics on the host (they operate on Python scalars and lists the caller owns):
@@ -143,6 +144,49 @@ def computeTmap(costMap, goal, start=None):
     """FastMarching.py:92-112 -> arrival-time field T (float64, inf = unreached)."""
     cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
     T = _ctx().tmap2d(cost, _node(goal), dtype=_DTYPE)
+    return T.astype(np.float64, copy=False)
+
+
+_MAX_RECTS = 1024  # eik_fim2d_update's limit
+
+
+def _mask_rects(mask, block=64, limit=_MAX_RECTS):
+    """The bounding box of a boolean (H, W) mask's True cells per block x block cells -> (x0, y0, x1, y1).
+    A mask that touches more than `limit` blocks is boxed per block of twice the side, and so on: fewer,
+    larger rectangles, which only invalidate more (every changed cell stays covered)."""
+    mask = np.asarray(mask, dtype=bool)
+    while True:
+        rects = []
+        for y0 in range(0, mask.shape[0], block):
+            rows = mask[y0:y0 + block]
+            if not rows.any():
+                continue
+            for x0 in range(0, mask.shape[1], block):
+                ys, xs = np.nonzero(rows[:, x0:x0 + block])
+                if len(ys):
+                    rects.append((x0 + int(xs.min()), y0 + int(ys.min()), x0 + int(xs.max()) + 1, y0 + int(ys.max()) + 1))
+        if len(rects) <= limit:
+            return rects
+        block *= 2
+
+
+def updateTmap(costMap, Tmap, goal, changed):
+    """No reference counterpart: the field computeTmap(costMap, goal) would return, from Tmap -- the
+    field computeTmap returned for an earlier costMap that differs from this one only inside `changed`,
+    a list of at most 1024 (x0, y0, x1, y1) rectangles (half-open) or a boolean (H, W) mask of the
+    changed cells (boxed per 64 x 64 block, per larger blocks if that gives more than 1024 rectangles).
+    Only the cells whose old value depended on a changed cell are solved again.
+    The inputs are not modified; the result is float64."""
+    cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
+    if np.shape(Tmap) != cost.shape:
+        raise ValueError(f"updateTmap: Tmap has shape {np.shape(Tmap)}, costMap {cost.shape}")
+    ch = np.asarray(changed)
+    if ch.dtype == bool and ch.shape != cost.shape:
+        raise ValueError(f"updateTmap: the mask has shape {ch.shape}, costMap {cost.shape}")
+    rects = _mask_rects(ch) if ch.dtype == bool and ch.shape == cost.shape else [tuple(int(v) for v in r) for r in changed]
+    if not rects:
+        return np.array(Tmap, dtype=np.float64, order="C")
+    T = _ctx().tmap2d_update(cost, np.ascontiguousarray(Tmap, dtype=_DTYPE), _node(goal), rects, dtype=_DTYPE)
     return T.astype(np.float64, copy=False)
 
 

@@ -109,6 +109,33 @@ int fim2d_persist_resident(bool f64, int cus, bool wide = false);
 hipError_t fim2d_merge_ghost(const Fim2dArgs& a, bool f64, int side, const void* recv, int64_t len, hipStream_t st);
 hipError_t fim2d_pack_edges(const Fim2dArgs& a, bool f64, void* n, void* s, void* w, void* e, hipStream_t st);
 
+// Incremental re-solve after local cost changes (replan.hip; one map, persistent mode).
+constexpr int kChangeAny = 0, kChangeLowered = 1;  // EIK_CHANGE_*
+constexpr int kMaxRects = 1024;
+struct ReplanRect {
+    int32_t x0, y0, x1, y1;  // half-open, clipped to the raster, non-empty
+    int32_t kind, pad;
+};
+struct ReplanArgs {
+    const ReplanRect* rects;   // [K], device
+    int K;
+    int64_t gx, gy;            // the goal: never a seed, never marked (by value: no load on a tile visit's path)
+    int* rlist;                // [tiles] the tiles the cone reaches, info[1] of them
+    unsigned* rflag;           // [tiles] 1: listed
+    // [0] cells invalidated, [1] tiles marked, [2] flood tile visits, [3] tiles queued for the solve
+    unsigned long long* info;  // [6], device
+};
+// phase 0: before the flood; 1: before the restart (queue words as after fim2d_init, T kept)
+hipError_t replan_prep(const Fim2dArgs& a, const ReplanArgs& r, int phase, hipStream_t st);
+hipError_t replan_seed(const Fim2dArgs& a, const ReplanArgs& r, bool f64, hipStream_t st);
+// a: the FIFO form of the solver's queue (bctl == nullptr, fresh_first == 0)
+hipError_t replan_flood(const Fim2dArgs& a, const ReplanArgs& r, bool f64, int grid, hipStream_t st);
+int replan_flood_resident(bool f64, int cus);
+// marked cells -> +inf over the recorded tiles, then the solve's first tiles queued (a: the solve's form)
+hipError_t replan_reset(const Fim2dArgs& a, const ReplanArgs& r, bool f64, hipStream_t st);
+// edge-column copies and kVisited from a field the caller binds as converged
+hipError_t replan_adopt(const Fim2dArgs& a, bool f64, hipStream_t st);
+
 // Layered solver (fim2dl.hip): a [H][W][ls] volume, layers z0 .. z0+nl-1 (fp32: nl <= 4, tiles of
 // 64 x 64; fp64: nl <= 3, tiles of fim2dl_rows(true) = 40 rows x 64 columns), on the 2D tile engine
 // (persistent mode only; a.ls / a.z0 set, no ghosts, no ordering window; a.nty counts tiles of

@@ -233,6 +233,14 @@ struct eik_fim2d {
     bool need_rewind = false;            // a launch without its queue rewind ran since the last init
     bool band_overflow = false;          // the last launch stopped on a full priority band (qerror bit 4)
     bool no_bands = false;               // ... so this solver's next starts use the FIFO
+    int64_t last_active = -1;            // tiles left by the last persistent launch read back (-1: none yet, or it failed)
+    // incremental re-solve (replan.hip): descriptors (pinned + device), recorded tiles, counters
+    DevBuf rp_rects, rp_list, rp_flag, rp_info;
+    ReplanRect* h_rects = nullptr;       // pinned [kMaxRects]
+    unsigned long long* h_info = nullptr;  // pinned [6]
+    hipEvent_t ev_rp[2] = {nullptr, nullptr};
+    bool rp_timed = false, rp_fallback = false;  // events recorded; the last resolve ended in a full solve
+    int flood_grid = 0;                  // co-resident workgroups of the flood kernel
     int persist_grid = 0;                // co-resident workgroups of the persistent kernel
     bool persist_wide = false;           // ... of which form (EIK_OPT_WIDE can change it between solves)
     // live domain decomposition: hold word on the device, mailbox of the halo agent on the host
@@ -593,6 +601,10 @@ void eik_fim2d_destroy(eik_fim2d* f) {
     if (f->ev_start) (void)hipEventDestroy(f->ev_start);
     if (f->ev_stop) (void)hipEventDestroy(f->ev_stop);
     if (f->box) (void)hipHostFree(f->box);
+    if (f->h_rects) (void)hipHostFree(f->h_rects);
+    if (f->h_info) (void)hipHostFree(f->h_info);
+    for (hipEvent_t ev : f->ev_rp)
+        if (ev) (void)hipEventDestroy(ev);
     for (auto ev : f->ev_pool) (void)hipEventDestroy(ev);
     delete f;
 }
@@ -615,8 +627,10 @@ int eik_fim2d_set_ghosts(eik_fim2d* f, void* n, void* s, void* w, void* e) {
     return EIK_OK;
 }
 
-int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
-    if (!f || !d_cost || !d_T || !goals) return EIK_ERR_ARG;
+// Bind the buffers and the stream and set a solve's options, budgets and priority bands: everything of
+// eik_fim2d_start but the goals' upload and the init / seed kernels (eik_fim2d_update and
+// eik_fim2d_adopt restart a solve without wiping T).
+static int fim2d_configure(eik_fim2d* f, const void* d_cost, void* d_T, void* stream) {
     eik_ctx* c = f->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     f->stream = (hipStream_t)stream;  // as given: NULL is the default (null) stream
@@ -659,9 +673,6 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     f->solve_ms = 0.0;
     f->ev_used = 0;
     HIPCHK(c, hipEventRecord(f->ev_start, f->stream));
-    // (the previous solve on this solver synchronised before returning: h_goals is free)
-    memcpy(f->h_goals, goals, sizeof(int64_t) * 2 * f->B);
-    HIPCHK(c, hipMemcpyAsync(f->goals.p, f->h_goals, sizeof(int64_t) * 2 * f->B, hipMemcpyHostToDevice, f->stream));
     // priority bands (persistent mode): kBands rings of twice the tiles each (a pending tile has at
     // most one live entry per band it was pushed to plus stale ones, dropped when taken), cleared
     // with the queue before the seed kernel pushes the goal's tile
@@ -695,12 +706,29 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
         f->a.disp = c->prio_dispatch > 0 ? (unsigned)c->prio_dispatch
                                          : f->a.tiles_per_map >= kWideTiles ? 128u : 16u;  // (fim_engine.hpp band_dispatch)
     }
-    HIPCHK(c, fim2d_init(f->a, f->f64, (int)f->B, (const int64_t*)f->goals.p, (unsigned*)f->edge.p, f->stream));
     // eik_last_form (the launch fills in the kernel's form)
     c->last_form[0] = 0;
     c->last_form[1] = f->a.bctl != nullptr;
     c->last_form[2] = f->a.max_passes;
     c->last_form[3] = f->a.bctl ? (int64_t)f->a.disp : 0;
+    f->last_active = -1;  // unknown until a launch's queue words are read back
+    return EIK_OK;
+}
+
+static int upload_goals(eik_fim2d* f, const int64_t* goals) {
+    // (the previous solve on this solver synchronised before returning: h_goals is free)
+    memcpy(f->h_goals, goals, sizeof(int64_t) * 2 * f->B);
+    HIPCHK(f->ctx, hipMemcpyAsync(f->goals.p, f->h_goals, sizeof(int64_t) * 2 * f->B, hipMemcpyHostToDevice, f->stream));
+    return EIK_OK;
+}
+
+int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
+    if (!f || !d_cost || !d_T || !goals) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    int rc = fim2d_configure(f, d_cost, d_T, stream);
+    if (!rc) rc = upload_goals(f, goals);
+    if (rc) return rc;
+    HIPCHK(c, fim2d_init(f->a, f->f64, (int)f->B, (const int64_t*)f->goals.p, (unsigned*)f->edge.p, f->stream));
     f->started = true;
     f->need_rewind = false;  // the init cleared the queue words
     return EIK_OK;
@@ -720,6 +748,7 @@ static int persist_result(eik_fim2d* f, int64_t* active) {
     if (err & 2u)
         return set_err(c, EIK_ERR_NOCONVERGE, "no convergence within %llu tile visits (negative costs?)",
                        (unsigned long long)f->a.qbudget);
+    f->last_active = f->h_q[128 / 4];
     if (active) *active = f->h_q[128 / 4];
     return EIK_OK;
 }
@@ -971,6 +1000,171 @@ int eik_fim2d_solve(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     if (active != 0)
         return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence after %ld iterations (negative costs?)",
                        (long)f->iterations);
+    return EIK_OK;
+}
+
+// ---- incremental re-solve after local cost changes (replan.hip)
+// What the update, its restart and adopt apply to: one map, no ghost strips, not a layered block, no
+// live launch, the persistent mode on a raster within its 32-bit offsets.
+static int replan_gate(eik_fim2d* f, const char* who) {
+    eik_ctx* c = f->ctx;
+    if (f->B != 1) return set_err(c, EIK_ERR_ARG, "%s needs one map (B = %ld)", who, (long)f->B);
+    if (f->lnl) return set_err(c, EIK_ERR_ARG, "%s: not for a layered block", who);
+    if (f->a.ghost[0] || f->a.ghost[1] || f->a.ghost[2] || f->a.ghost[3])
+        return set_err(c, EIK_ERR_ARG, "%s: not for a domain-decomposition block (ghost strips are bound)", who);
+    if (f->live_on) return set_err(c, EIK_ERR_ARG, "%s: a live launch is still running (eik_fim2d_release)", who);
+    if (c->mode != kModePersistent || c->delta > 0)
+        return set_err(c, EIK_ERR_ARG, "%s needs the persistent mode (EIK_OPT_MODE, no EIK_OPT_DELTA)", who);
+    if (f->H * f->W * (f->f64 ? 8 : 4) >= (int64_t)UINT32_MAX)
+        return set_err(c, EIK_ERR_ARG, "%s: the raster is past the persistent mode's 32-bit offsets", who);
+    return EIK_OK;
+}
+
+static int replan_buffers(eik_fim2d* f, ReplanArgs* r) {
+    eik_ctx* c = f->ctx;
+    const size_t tiles = (size_t)f->a.capacity;
+    HIPCHK(c, f->rp_rects.ensure(sizeof(ReplanRect) * kMaxRects));
+    HIPCHK(c, f->rp_list.ensure(sizeof(int) * tiles));
+    HIPCHK(c, f->rp_flag.ensure(sizeof(unsigned) * tiles));
+    HIPCHK(c, f->rp_info.ensure(64));
+    if (!f->h_rects) HIPCHK(c, hipHostMalloc((void**)&f->h_rects, sizeof(ReplanRect) * kMaxRects));
+    if (!f->h_info) {
+        HIPCHK(c, hipHostMalloc((void**)&f->h_info, 64));
+        memset(f->h_info, 0, 64);
+    }
+    for (hipEvent_t& ev : f->ev_rp)
+        if (!ev) HIPCHK(c, hipEventCreate(&ev));
+    r->rects = (const ReplanRect*)f->rp_rects.p;
+    r->K = 0;
+    r->gx = f->h_goals[0];  // (the goals of the last start / adopt)
+    r->gy = f->h_goals[1];
+    r->rlist = (int*)f->rp_list.p;
+    r->rflag = (unsigned*)f->rp_flag.p;
+    r->info = (unsigned long long*)f->rp_info.p;
+    return EIK_OK;
+}
+
+int eik_fim2d_update(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    int rc = replan_gate(f, "eik_fim2d_update");
+    if (rc) return rc;
+    if (!f->started || !f->a.cost || !f->a.T)
+        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the solver was never started or adopted");
+    if (f->a.mode != kModePersistent)
+        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the bound solve did not run in the persistent mode");
+    if (f->last_active != 0)
+        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the last solve did not end converged (0 active tiles)");
+    if (K < 0 || K > kMaxRects) return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: K = %ld outside [0, %d]", (long)K, kMaxRects);
+    if (K > 0 && !rects) return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rects is NULL");
+    std::vector<ReplanRect> v((size_t)K);
+    bool any = false;
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t x0 = rects[4 * k], y0 = rects[4 * k + 1], x1 = rects[4 * k + 2], y1 = rects[4 * k + 3];
+        const int kind = kinds ? kinds[k] : kChangeAny;
+        if (kind != kChangeAny && kind != kChangeLowered)
+            return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rectangle %ld has kind %d (0 or 1)", (long)k, kind);
+        if (x1 <= x0 || y1 <= y0)
+            return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rectangle %ld (%ld, %ld, %ld, %ld) is empty", (long)k, (long)x0,
+                           (long)y0, (long)x1, (long)y1);
+        const int64_t cx0 = std::max<int64_t>(x0, 0), cy0 = std::max<int64_t>(y0, 0);
+        const int64_t cx1 = std::min<int64_t>(x1, f->W), cy1 = std::min<int64_t>(y1, f->H);
+        if (cx1 <= cx0 || cy1 <= cy0)
+            return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rectangle %ld (%ld, %ld, %ld, %ld) lies outside %ldx%ld", (long)k,
+                           (long)x0, (long)y0, (long)x1, (long)y1, (long)f->H, (long)f->W);
+        v[k] = ReplanRect{(int32_t)cx0, (int32_t)cy0, (int32_t)cx1, (int32_t)cy1, kind, 0};
+        any |= kind == kChangeAny;
+    }
+    ReplanArgs r{};
+    rc = replan_buffers(f, &r);
+    // options, budgets and the priority bands (their width from the NEW cost) as eik_fim2d_start sets them
+    if (!rc) rc = fim2d_configure(f, f->a.cost, f->a.T, stream);
+    if (rc) return rc;
+    r.K = (int)K;
+    if (K > 0) {  // (the last update's copy has completed: a solve synchronised since)
+        memcpy(f->h_rects, v.data(), sizeof(ReplanRect) * (size_t)K);
+        HIPCHK(c, hipMemcpyAsync(f->rp_rects.p, f->h_rects, sizeof(ReplanRect) * (size_t)K, hipMemcpyHostToDevice, f->stream));
+    }
+    // the flood runs on the plain FIFO of the solver's queue
+    Fim2dArgs fa = f->a;
+    fa.bctl = nullptr;
+    fa.fresh_first = 0;
+    fa.qhold = nullptr;
+    fa.live = nullptr;
+    fa.edge_dirty = nullptr;
+    HIPCHK(c, hipEventRecord(f->ev_rp[0], f->stream));
+    HIPCHK(c, replan_prep(fa, r, 0, f->stream));
+    if (any) {
+        if (f->flood_grid == 0) f->flood_grid = replan_flood_resident(f->f64, c->cu_count);
+        const int g = std::max(1, std::min(c->grid > 0 ? c->grid : 4 * c->cu_count, f->flood_grid));
+        HIPCHK(c, replan_seed(fa, r, f->f64, f->stream));
+        HIPCHK(c, replan_flood(fa, r, f->f64, g, f->stream));
+    }
+    HIPCHK(c, replan_prep(f->a, r, 1, f->stream));
+    if (K > 0) HIPCHK(c, replan_reset(f->a, r, f->f64, f->stream));
+    HIPCHK(c, hipEventRecord(f->ev_rp[1], f->stream));
+    HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    f->rp_timed = true;
+    f->rp_fallback = false;
+    f->need_rewind = false;  // the prep cleared the queue words
+    if (K == 0) f->last_active = 0;  // nothing queued: still converged
+    return EIK_OK;
+}
+
+int eik_fim2d_resolve(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
+    int rc = eik_fim2d_update(f, rects, kinds, K, stream);
+    if (rc) return rc;
+    int64_t active = 0;
+    f->defer_sync = true;
+    rc = eik_fim2d_iterate(f, f->max_iters, &active);
+    f->defer_sync = false;
+    if (!rc) rc = finish_solve(f, &active);
+    if (rc && f->band_overflow) {  // a priority band's ring was full: a full solve on the FIFO
+        f->band_overflow = false;
+        f->no_bands = true;
+        const int64_t g[2] = {f->h_goals[0], f->h_goals[1]};
+        rc = eik_fim2d_solve(f, f->a.cost, f->a.T, g, stream);
+        f->rp_fallback = true;
+        return rc;
+    }
+    if (rc) return rc;
+    if (active != 0)
+        return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence of the re-solve (%ld tiles left; negative costs?)", (long)active);
+    return EIK_OK;
+}
+
+int eik_fim2d_adopt(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    if (!d_cost || !d_T || !goals) return set_err(c, EIK_ERR_ARG, "eik_fim2d_adopt: NULL argument");
+    int rc = replan_gate(f, "eik_fim2d_adopt");
+    if (rc) return rc;
+    ReplanArgs r{};
+    rc = replan_buffers(f, &r);
+    if (!rc) rc = fim2d_configure(f, d_cost, d_T, stream);
+    if (!rc) rc = upload_goals(f, goals);
+    if (rc) return rc;
+    HIPCHK(c, replan_adopt(f->a, f->f64, f->stream));
+    HIPCHK(c, replan_prep(f->a, r, 0, f->stream));  // the queue as after a converged solve
+    HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    f->rp_timed = false;
+    f->rp_fallback = false;
+    f->started = true;
+    f->need_rewind = false;
+    f->last_active = 0;
+    return EIK_OK;
+}
+
+int eik_fim2d_update_info(eik_fim2d* f, int64_t out[6]) {
+    if (!f || !out) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (!f->h_info) return EIK_OK;  // no update yet
+    HIPCHK(c, hipStreamSynchronize(f->stream));
+    for (int i = 0; i < 4; ++i) out[i] = (int64_t)f->h_info[i];
+    float ms = 0.f;
+    if (f->rp_timed && hipEventElapsedTime(&ms, f->ev_rp[0], f->ev_rp[1]) == hipSuccess) out[4] = (int64_t)(ms * 1000.0f + 0.5f);
+    out[5] = f->rp_fallback ? 1 : 0;
     return EIK_OK;
 }
 
@@ -1327,7 +1521,45 @@ static int tmap_host(eik_ctx* c, const R* cost, int64_t B, int64_t H, int64_t W,
     return EIK_OK;
 }
 
+// cost_new and the converged field of the earlier cost go up; adopt + resolve on the cached solver
+template <typename R>
+static int tmap_update_host(eik_ctx* c, const R* cost, R* T, int64_t H, int64_t W, int64_t gx, int64_t gy,
+                            const int64_t* rects, const int* kinds, int64_t K) {
+    if (!c || !cost || !T || H < 1 || W < 1) return c ? set_err(c, EIK_ERR_ARG, "bad arguments") : EIK_ERR_ARG;
+    if (gx < 0 || gy < 0 || gx >= W || gy >= H)
+        return set_err(c, EIK_ERR_ARG, "goal (%ld, %ld) outside %ldx%ld", (long)gx, (long)gy, (long)H, (long)W);
+    const int64_t n = H * W;
+    HIPCHK(c, hipSetDevice(c->device));
+    eik_fim2d* f = nullptr;
+    int rc = get_solver(c, 1, H, W, sizeof(R) == 8 ? EIK_F64 : EIK_F32, &f);
+    if (!rc) rc = replan_gate(f, "eik_tmap2d_update");
+    if (rc) return rc;
+    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
+    HIPCHK(c, c->T.ensure(sizeof(R) * n));
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
+    HIPCHK(c, host_to_dev(c, c->T.p, T, sizeof(R) * n, c->stream));
+    rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (rc) return rc;
+    const int64_t g[2] = {gx, gy};
+    rc = eik_fim2d_adopt(f, c->cost.p, c->T.p, g, c->stream);
+    if (!rc) rc = eik_fim2d_resolve(f, rects, kinds, K, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
 extern "C" {
+
+int eik_tmap2d_update_f32(eik_ctx* c, const float* cost_new, float* T, int64_t H, int64_t W, int64_t gx, int64_t gy,
+                          const int64_t* rects, const int* kinds, int64_t K) {
+    return tmap_update_host<float>(c, cost_new, T, H, W, gx, gy, rects, kinds, K);
+}
+
+int eik_tmap2d_update_f64(eik_ctx* c, const double* cost_new, double* T, int64_t H, int64_t W, int64_t gx, int64_t gy,
+                          const int64_t* rects, const int* kinds, int64_t K) {
+    return tmap_update_host<double>(c, cost_new, T, H, W, gx, gy, rects, kinds, K);
+}
 
 int eik_tmap2d_f32(eik_ctx* c, const float* cost, int64_t H, int64_t W, int64_t gx, int64_t gy, float* T) {
     const int64_t g[2] = {gx, gy};

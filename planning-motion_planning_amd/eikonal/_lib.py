@@ -203,8 +203,29 @@ def lib():
                                            i64, _i64p, _i32p]
         L.eik_plan2d_batch_f32.argtypes = [vp, _f32p, i64, i64, i64, _i64p, _f64p, C.c_double, _f64p, i64, _i64p,
                                            _i32p, vp]
+        # incremental re-solve: rects / kinds are nullable host arrays (passed as an address or None)
+        L.eik_fim2d_update.argtypes = [vp, vp, vp, i64, vp]
+        L.eik_fim2d_resolve.argtypes = [vp, vp, vp, i64, vp]
+        L.eik_fim2d_adopt.argtypes = [vp, vp, vp, _i64p, vp]
+        L.eik_fim2d_update_info.argtypes = [vp, _i64p]
+        L.eik_tmap2d_update_f32.argtypes = [vp, _f32p, _f32p, i64, i64, i64, i64, vp, vp, i64]
+        L.eik_tmap2d_update_f64.argtypes = [vp, _f64p, _f64p, i64, i64, i64, i64, vp, vp, i64]
         _lib = L
         return L
+
+
+CHANGE_ANY, CHANGE_LOWERED = 0, 1  # eik_change: the kind of a changed rectangle (eik_fim2d_update)
+
+
+def _rects(rects, kinds):
+    """(rects int64 [K][4], kinds int32 [K] or None, K) as host arrays for the update entry points"""
+    r = np.ascontiguousarray(rects, dtype=np.int64).reshape(-1, 4)
+    k = None
+    if kinds is not None:
+        k = np.ascontiguousarray(kinds, dtype=np.int32).reshape(-1)
+        if len(k) != len(r):
+            raise ValueError(f"{len(r)} rectangles but {len(k)} kinds")
+    return r, k, len(r)
 
 
 EXPORTED = [
@@ -223,6 +244,8 @@ EXPORTED = [
     "eik_fim3dl_create", "eik_fim3dl_start", "eik_last_form",
     "eik_path2d_batch_dev", "eik_path2d_batch_f64", "eik_path3d_batch_dev", "eik_path3d_batch_f64",
     "eik_plan2d_batch_f32",
+    "eik_fim2d_update", "eik_fim2d_resolve", "eik_fim2d_adopt", "eik_fim2d_update_info",
+    "eik_tmap2d_update_f32", "eik_tmap2d_update_f64",
 ]
 
 
@@ -332,6 +355,23 @@ class Context:
         fn = lib().eik_tmap2d_f64 if cost.dtype == np.float64 else lib().eik_tmap2d_f32
         self._chk(fn(self._h, cost, H, W, int(goal[0]), int(goal[1]), T))
         return T
+
+    def tmap2d_update(self, cost, T, goal, rects, kinds=None, dtype=np.float64):
+        """The field of `cost` from T, the converged field of an earlier cost of the same raster that
+        differs from `cost` only inside `rects` [(x0, y0, x1, y1), ...] (half-open; kinds: CHANGE_ANY /
+        CHANGE_LOWERED per rectangle, None = all ANY).  Only what depended on the raised cells is solved
+        again (eik_tmap2d_update_*).  The inputs are not modified."""
+        cost = np.ascontiguousarray(cost, dtype=dtype)
+        H, W = cost.shape
+        if np.shape(T) != cost.shape:
+            raise ValueError(f"tmap2d_update: T has shape {np.shape(T)}, cost {cost.shape}")
+        out = result_empty(cost.shape, cost.dtype)
+        out[...] = T
+        r, k, K = _rects(rects, kinds)
+        fn = lib().eik_tmap2d_update_f64 if cost.dtype == np.float64 else lib().eik_tmap2d_update_f32
+        self._chk(fn(self._h, cost, out, H, W, int(goal[0]), int(goal[1]), r.ctypes.data if K else None,
+                     k.ctypes.data if k is not None and K else None, K))
+        return out
 
     def tmap2d_batch(self, costs, goals):
         costs = np.ascontiguousarray(costs, dtype=np.float32)
@@ -644,6 +684,29 @@ class Fim2d:
         s = EikStats()
         self.ctx._chk(lib().eik_fim2d_stats(self._h, C.byref(s)))
         return s.as_dict()
+
+    # incremental re-solve after local cost changes (eik_fim2d_update / resolve / adopt / update_info)
+    def update(self, rects, kinds=None, stream=None):
+        """asynchronous: invalidate what depended on the changed rectangles and queue the restart;
+        iterate() converges it"""
+        r, k, K = _rects(rects, kinds)
+        self.ctx._chk(lib().eik_fim2d_update(self._h, r.ctypes.data if K else None,
+                                             k.ctypes.data if k is not None and K else None, K, stream))
+
+    def resolve(self, rects, kinds=None, stream=None):
+        r, k, K = _rects(rects, kinds)
+        self.ctx._chk(lib().eik_fim2d_resolve(self._h, r.ctypes.data if K else None,
+                                              k.ctypes.data if k is not None and K else None, K, stream))
+
+    def adopt(self, d_cost, d_T, goals, stream=None):
+        self.ctx._chk(lib().eik_fim2d_adopt(self._h, d_cost, d_T, np.ascontiguousarray(goals, np.int64).reshape(-1),
+                                            stream))
+
+    def update_info(self):
+        o = np.zeros(6, np.int64)
+        self.ctx._chk(lib().eik_fim2d_update_info(self._h, o))
+        return dict(zip(("cells", "tiles_marked", "flood_visits", "tiles_queued", "device_us", "fell_back"),
+                        (int(v) for v in o)))
 
     # live domain decomposition (eik_fim2d_live_bind / launch / live_pack / live_merge / release)
     def live_bind(self, send, recv):
