@@ -329,6 +329,66 @@ int eik_tmap2d_update_f32(eik_ctx* ctx, const float* cost_new, float* T_inout, i
 int eik_tmap2d_update_f64(eik_ctx* ctx, const double* cost_new, double* T_inout, int64_t H, int64_t W, int64_t gx,
                           int64_t gy, const int64_t* rects, const int* kinds, int64_t K);
 
+/* Multi-source 2D solves (no reference counterpart): the field of a SET of K seeds,
+ * seed k at cell (x, y) of map map_of[k] with start value t0[k] >= 0,
+ *     T = min_k (t0[k] + cost-to-go from seed k)
+ * as the solver's own discrete fixed point -- which lies below the pointwise minimum of K single-source
+ * fields wherever a cell takes its x neighbour from one seed's wave and its y neighbour from another's.
+ * A goal region, several candidate goals, a docking line; t0 carries a cost already spent elsewhere.
+ * Two seeds may name one cell (the lower t0 holds); a seed that another seed's wave undercuts is
+ * dominated (T there ends below its t0).  A seed on a +inf-cost cell keeps its t0.
+ *
+ * seeds: K x (x, y), host.  t0: K host doubles, rounded to the solver's dtype, or NULL (all 0).  map_of:
+ * K host int32, or NULL (needs B == 1).  The host arrays are read before the call returns and go to the
+ * device in stream order through a pinned block.  Options, statistics, the visit budget, the priority
+ * bands (the seeds' keys are their t0) and eik_last_form behave as in any solve.
+ *
+ * EIK_ERR_ARG, with a message naming the offending index and nothing launched: K < 1 or K > 2^24, a
+ * NULL pointer, a seed outside the raster (stricter than the single goal, whose "outside = seeds
+ * nothing" exists for decomposition blocks), map_of[k] outside [0, B), map_of == NULL with B > 1, a t0
+ * that is negative, NaN or +inf or (fp32 solver) rounds to +inf, a layered block, a solver with ghost
+ * strips bound.
+ *
+ * eik_fim2d_start_seeds  asynchronous; eik_fim2d_iterate then converges it.
+ * eik_fim2d_solve_seeds  start + iterate to convergence (synchronous); a full priority-band ring falls
+ *                        back to the FIFO with the same seeds, as in eik_fim2d_solve.
+ * The incremental re-solve knows one goal: after a seeded start, eik_fim2d_update, eik_fim2d_resolve and
+ * eik_tmap2d_update_* (the context's cached solver after eik_tmap2d_seeds_*) return EIK_ERR_ARG ("the
+ * bound solve has a seed set") until an eik_fim2d_start / eik_fim2d_solve / eik_fim2d_adopt (any
+ * single-goal host solve on the context) binds a single-goal solve again.
+ * Not covered: 3D and layered solves, the bidirectional fronts, a seeded eik_plan2d_batch. */
+int eik_fim2d_start_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                          const int32_t* map_of, int64_t K, void* stream);
+int eik_fim2d_solve_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                          const int32_t* map_of, int64_t K, void* stream);
+
+/* Nearest-seed labels: which seed does each cell of a converged field belong to (the nearest goal
+ * under the cost, the Voronoi partition of the seeds, the `end` to pass to getPathGDM for a start).
+ * d_T: the converged field of B maps of H x W in dtype (fewer than 2^31 cells in all), device; seeds,
+ * t0, map_of, K: the seed list that produced it, checked as above; d_label: int32 [B][H][W], device.
+ * Asynchronous on `stream`, no read-back.  The context owns the scratch: calls on one stream simply
+ * queue up, calls on different streams must not overlap.
+ * The rule:
+ *   Root.   Cell c is a root with label k when seed k lies on c and T[c] == (R)t0_k bit for bit.  Of
+ *           several such k, the lowest wins.  A seed that another seed's wave undercut
+ *           (T[c] < t0_k) is not a root.
+ *   Parent. Otherwise, the parent of a finite cell is its 4-neighbour with the smallest T strictly
+ *           below T[c].  Among equal candidates the first in the order x-1, x+1, y-1, y+1 wins.  The
+ *           label of c is the label of its parent.
+ *   Unlabelled cells.  label = -1 for: a cell with T = +inf; a finite non-root cell with no strictly
+ *           lower neighbour (a zero-cost plateau, or fp32 rounding of T + c to T); everything whose
+ *           parent chain ends in such a cell.
+ * Parents strictly decrease T, so they form a forest; the labels are a deterministic function of T and
+ * the seed list. */
+int eik_labels2d_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, const int64_t* seeds,
+                     const double* t0, const int32_t* map_of, int64_t K, int32_t* d_label, void* stream);
+
+/* Host buffers, one map: cost in, the seeded field T and (labels != NULL) its labels out. */
+int eik_tmap2d_seeds_f32(eik_ctx* ctx, const float* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
+                         int64_t K, float* T, int32_t* labels);
+int eik_tmap2d_seeds_f64(eik_ctx* ctx, const double* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
+                         int64_t K, double* T, int32_t* labels);
+
 /* Live domain decomposition (no reference counterpart: the multi-GPU split of SURVEY.md §8(e)).
  * eik_fim2d_launch(fim, 1) starts ONE persistent launch on the bound stream and returns at once.
  * Its last workgroup is a halo agent serving a pinned host mailbox while the others solve; the

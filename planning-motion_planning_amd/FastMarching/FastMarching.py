@@ -11,6 +11,8 @@ the gradient and the path extraction run on the GPU (libeikonal.so via ctypes):
 Additions with no reference counterpart:
   getPathsGDM(T, inits, end, tau)        many getPathGDM walks on one field in one GPU launch
   updateTmap(costMap, Tmap, goal, changed)  computeTmap's field after local cost changes, from the old field
+  computeTmapMulti(costMap, goals, offsets, labels)  the field of a goal set with start values (+ nearest-goal labels)
+  getPathsToNearest(T, labels, goals, inits, tau)    each start's path to the goal its cell belongs to, one launch
 
 Scalar/list helpers that the reference exposes at module level keep their reference
 semantics on the host (they operate on Python scalars and lists the caller owns):
@@ -223,6 +225,62 @@ def getPathsGDM(totalCostMap, initWaypoints, endWaypoint, tau):
     bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
     if bad:
         raise IndexError(f"getPathsGDM: the descent of path {bad[0]} left the field (getPathGDM raises here too)")
+    return [path for path, _ in res]
+
+
+def _goal_list(goals, shape):
+    """goals as a (K, 2) int64 array of nodes (x, y): a list of nodes, or a boolean mask of `shape` whose
+    True cells are the seeds in row-major order"""
+    g = np.asarray(goals)
+    if g.dtype == bool:
+        if g.shape != tuple(shape):
+            raise ValueError(f"computeTmapMulti: the mask has shape {g.shape}, costMap {tuple(shape)}")
+        ys, xs = np.nonzero(g)  # row-major
+        return np.stack([xs, ys], axis=1).astype(np.int64)
+    if g.ndim != 2 or g.shape[1] < 2:
+        raise ValueError(f"computeTmapMulti: goals must be K nodes (x, y) or a boolean mask, not shape {g.shape}")
+    return np.ascontiguousarray(g[:, :2], dtype=np.int64)
+
+
+def computeTmapMulti(costMap, goals, offsets=None, labels=False):
+    """No reference counterpart: the arrival-time field of a goal SET, min over the goals of (offset +
+    cost-to-go), solved as one problem.  goals: K nodes (x, y), or a boolean mask of
+    costMap's shape (its True cells, row-major); offsets: K start values >= 0 (None: all 0).  Returns T
+    (float64), or with labels=True (T, labels): int32, the index into goals of the goal each cell
+    belongs to, -1 for unreached cells."""
+    cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
+    g = _goal_list(goals, cost.shape)
+    if len(g) == 0:
+        raise ValueError("computeTmapMulti: no goal")
+    res = _ctx().tmap2d_seeds(cost, g, offsets, dtype=_DTYPE, labels=labels)
+    if labels:
+        return res[0].astype(np.float64, copy=False), res[1]
+    return res.astype(np.float64, copy=False)
+
+
+def getPathsToNearest(totalCostMap, labels, goals, initWaypoints, tau):
+    """No reference counterpart: from every row of initWaypoints (P, 2), getPathGDM to the goal its cell
+    belongs to -- goals[labels[node(start)]], with (totalCostMap, labels) from computeTmapMulti(...,
+    labels=True) and the same goals -- in one launch -> a list of P (K, 2) float64 paths.  ValueError
+    names a start whose cell has no label (-1: unreached); IndexError as getPathsGDM."""
+    T = np.ascontiguousarray(totalCostMap, dtype=np.float64)
+    lab = np.asarray(labels)
+    if lab.shape != T.shape:
+        raise ValueError(f"getPathsToNearest: labels have shape {lab.shape}, the field {T.shape}")
+    g = _goal_list(goals, T.shape)
+    inits = np.asarray(initWaypoints, dtype=np.float64)
+    inits = inits.reshape(-1, inits.shape[-1])[:, :2]
+    ends = np.empty_like(inits)
+    for p, s in enumerate(inits):
+        x, y = _node(s)
+        k = int(lab[y, x]) if 0 <= x < T.shape[1] and 0 <= y < T.shape[0] else -1
+        if k < 0 or k >= len(g):
+            raise ValueError(f"getPathsToNearest: start {p} ({x}, {y}) belongs to no goal (label {k})")
+        ends[p] = g[k]
+    res = _ctx().path2d_batch(T, inits, ends, float(tau))
+    bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
+    if bad:
+        raise IndexError(f"getPathsToNearest: the descent of path {bad[0]} left the field (getPathGDM raises here too)")
     return [path for path, _ in res]
 
 

@@ -136,6 +136,29 @@ hipError_t replan_reset(const Fim2dArgs& a, const ReplanArgs& r, bool f64, hipSt
 // edge-column copies and kVisited from a field the caller binds as converged
 hipError_t replan_adopt(const Fim2dArgs& a, bool f64, hipStream_t st);
 
+// Multi-source solves (seeds.hip): a seed set with start values, and the nearest-seed labels.
+constexpr int64_t kMaxSeeds = 1ll << 24;
+struct SeedDesc {
+    int32_t x, y, map, pad;  // inside the raster, 0 <= map < B
+    double t0;               // finite, >= 0 (never -0), already rounded to the solve's dtype
+};
+// after fim2d_init with no goal: T[seed] = min(T, t0) (and the edge columns' copy), the seeds' tiles and
+// the neighbours across the tile sides they lie on activated with key t0 (either mode)
+hipError_t fim2d_start_seeds(const Fim2dArgs& a, bool f64, const SeedDesc* d_seeds, int64_t K, hipStream_t st);
+constexpr int kLabelPasses = 32;  // pointer-jumping passes at most (n < 2^31 cells)
+struct LabelArgs {
+    const void* T;           // [B][H][W] converged field (R), device
+    int64_t H, W, n;         // n = B * H * W < 2^31
+    const SeedDesc* seeds;   // [K], device: the seeds that produced T
+    int K;
+    int* par;                // [n] scratch: parent, then the chain's end
+    int* label;              // [n] out
+    unsigned* flags;         // [kLabelPasses] scratch: pass p moved a pointer
+};
+// label[c] by the rule of include/eikonal.h (eik_labels2d_dev), asynchronous on st, no read-back
+hipError_t labels2d(const LabelArgs& l, bool f64, hipStream_t st);
+int labels2d_passes(int64_t H, int64_t W);  // the jump passes it launches: ceil(log2(H * W))
+
 // Layered solver (fim2dl.hip): a [H][W][ls] volume, layers z0 .. z0+nl-1 (fp32: nl <= 4, tiles of
 // 64 x 64; fp64: nl <= 3, tiles of fim2dl_rows(true) = 40 rows x 64 columns), on the 2D tile engine
 // (persistent mode only; a.ls / a.z0 set, no ghosts, no ordering window; a.nty counts tiles of

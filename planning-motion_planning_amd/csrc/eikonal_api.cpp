@@ -131,6 +131,23 @@ struct DescBlock {
     hipEvent_t ev = nullptr;
 };
 
+// The seeds of one multi-source call (eik_fim2d_start_seeds, eik_labels2d_dev): a pinned host block
+// and its device twin, grown on demand; ev marks the block's last upload (waited for before reuse).
+struct SeedStage {
+    SeedDesc* h = nullptr;
+    SeedDesc* d = nullptr;
+    int64_t cap = 0;
+    hipEvent_t ev = nullptr;
+    void release() {
+        if (h) (void)hipHostFree(h);
+        if (d) (void)hipFree(d);
+        if (ev) (void)hipEventDestroy(ev);
+        h = d = nullptr;
+        ev = nullptr;
+        cap = 0;
+    }
+};
+
 }  // namespace
 
 constexpr double kFrontsMargin = 1.25;  // capped bidirectional fronts (solve_fronts)
@@ -205,6 +222,8 @@ struct eik_ctx {
     CopyPool* pool = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t e3[2] = {nullptr, nullptr};
+    SeedStage lab_seeds;               // eik_labels2d_dev: its seeds, and its scratch (parents | pass flags)
+    DevBuf lab_work, lab_out;          // (lab_out: the host entries' device labels)
     std::vector<DescBlock> desc;       // batched paths: descriptor blocks in flight or free (stage_desc)
     size_t desc_next = 0;
 };
@@ -233,6 +252,9 @@ struct eik_fim2d {
     bool need_rewind = false;            // a launch without its queue rewind ran since the last init
     bool band_overflow = false;          // the last launch stopped on a full priority band (qerror bit 4)
     bool no_bands = false;               // ... so this solver's next starts use the FIFO
+    // a seed set started the bound solve (eik_fim2d_start_seeds): the re-solve knows one goal only
+    bool seeded = false;
+    SeedStage sd;                        // its seeds
     int64_t last_active = -1;            // tiles left by the last persistent launch read back (-1: none yet, or it failed)
     // incremental re-solve (replan.hip): descriptors (pinned + device), recorded tiles, counters
     DevBuf rp_rects, rp_list, rp_flag, rp_info;
@@ -421,6 +443,8 @@ void eik_destroy(eik_ctx* c) {
         if (b.h) (void)hipHostFree(b.h);
         if (b.d) (void)hipFree(b.d);
     }
+    if (c->lab_seeds.ev) (void)hipEventSynchronize(c->lab_seeds.ev);
+    c->lab_seeds.release();
     c->pool = nullptr;  // (the process-wide pool stays)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -603,6 +627,7 @@ void eik_fim2d_destroy(eik_fim2d* f) {
     if (f->box) (void)hipHostFree(f->box);
     if (f->h_rects) (void)hipHostFree(f->h_rects);
     if (f->h_info) (void)hipHostFree(f->h_info);
+    f->sd.release();
     for (hipEvent_t ev : f->ev_rp)
         if (ev) (void)hipEventDestroy(ev);
     for (auto ev : f->ev_pool) (void)hipEventDestroy(ev);
@@ -730,6 +755,83 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     if (rc) return rc;
     HIPCHK(c, fim2d_init(f->a, f->f64, (int)f->B, (const int64_t*)f->goals.p, (unsigned*)f->edge.p, f->stream));
     f->started = true;
+    f->seeded = false;
+    f->need_rewind = false;  // the init cleared the queue words
+    return EIK_OK;
+}
+
+// ---- multi-source solves (seeds.hip)
+// The host checks shared by the seeded start and the labels: on EIK_OK out holds the K descriptors,
+// t0 rounded to the dtype.  Every failure is EIK_ERR_ARG with the offending index; nothing is launched.
+static int seeds_check(eik_ctx* c, const char* who, int64_t B, int64_t H, int64_t W, bool f64, const int64_t* seeds,
+                       const double* t0, const int32_t* map_of, int64_t K, std::vector<SeedDesc>& out) {
+    if (K < 1 || K > kMaxSeeds) return set_err(c, EIK_ERR_ARG, "%s: K = %ld seeds (1 .. 2^24)", who, (long)K);
+    if (!seeds) return set_err(c, EIK_ERR_ARG, "%s: seeds is NULL", who);
+    if (!map_of && B != 1)
+        return set_err(c, EIK_ERR_ARG, "%s: map_of is NULL with B = %ld maps (B == 1 needed)", who, (long)B);
+    out.resize((size_t)K);
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t x = seeds[2 * k], y = seeds[2 * k + 1];
+        if (x < 0 || y < 0 || x >= W || y >= H)
+            return set_err(c, EIK_ERR_ARG, "%s: seed %ld (%ld, %ld) outside %ldx%ld", who, (long)k, (long)x, (long)y, (long)H,
+                           (long)W);
+        const int32_t m = map_of ? map_of[k] : 0;
+        if (m < 0 || m >= B) return set_err(c, EIK_ERR_ARG, "%s: map_of[%ld] = %d outside [0, %ld)", who, (long)k, m, (long)B);
+        double v = t0 ? t0[k] : 0.0;
+        if (!(v >= 0.0) || std::isinf(v))
+            return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g (finite and >= 0 needed)", who, (long)k, v);
+        if (!f64) {
+            v = (double)(float)v;
+            if (std::isinf(v)) return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g rounds to +inf in fp32", who, (long)k, t0[k]);
+        }
+        out[k] = SeedDesc{(int32_t)x, (int32_t)y, m, 0, v + 0.0};  // (+ 0.0: -0 -> +0, values order like their bits)
+    }
+    return EIK_OK;
+}
+
+// the checked seeds into the block's pinned half and on to the device in stream order
+static int seeds_upload(eik_ctx* c, SeedStage& s, const std::vector<SeedDesc>& v, hipStream_t st) {
+    const int64_t K = (int64_t)v.size();
+    if (!s.ev) HIPCHK(c, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventSynchronize(s.ev));  // the block's last upload (a never-recorded event is complete)
+    if (s.cap < K) {
+        if (s.h) (void)hipHostFree(s.h);
+        if (s.d) (void)hipFree(s.d);
+        s.h = s.d = nullptr;
+        s.cap = 0;
+        const int64_t cap = std::max<int64_t>(1024, K);
+        HIPCHK(c, hipHostMalloc((void**)&s.h, sizeof(SeedDesc) * cap));
+        HIPCHK(c, hipMalloc((void**)&s.d, sizeof(SeedDesc) * cap));
+        s.cap = cap;
+    }
+    memcpy(s.h, v.data(), sizeof(SeedDesc) * (size_t)K);
+    HIPCHK(c, hipMemcpyAsync(s.d, s.h, sizeof(SeedDesc) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(s.ev, st));
+    return EIK_OK;
+}
+
+int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                          const int32_t* map_of, int64_t K, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    const char* who = "eik_fim2d_start_seeds";
+    if (!d_cost || !d_T) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_cost ? "d_cost" : "d_T");
+    if (f->lnl) return set_err(c, EIK_ERR_ARG, "%s: not for a layered block", who);
+    if (f->a.ghost[0] || f->a.ghost[1] || f->a.ghost[2] || f->a.ghost[3])
+        return set_err(c, EIK_ERR_ARG, "%s: not for a domain-decomposition block (ghost strips are bound)", who);
+    std::vector<SeedDesc> v;
+    int rc = seeds_check(c, who, f->B, f->H, f->W, f->f64, seeds, t0, map_of, K, v);
+    if (!rc) rc = fim2d_configure(f, d_cost, d_T, stream);
+    if (rc) return rc;
+    // the ordinary init with no goal on any map (a goal outside the map seeds nothing), then the seeds
+    std::vector<int64_t> none(2 * (size_t)f->B, -1);
+    rc = upload_goals(f, none.data());
+    if (!rc) rc = seeds_upload(c, f->sd, v, f->stream);
+    if (rc) return rc;
+    HIPCHK(c, fim2d_init(f->a, f->f64, (int)f->B, (const int64_t*)f->goals.p, (unsigned*)f->edge.p, f->stream));
+    HIPCHK(c, fim2d_start_seeds(f->a, f->f64, f->sd.d, K, f->stream));
+    f->started = true;
+    f->seeded = true;
     f->need_rewind = false;  // the init cleared the queue words
     return EIK_OK;
 }
@@ -1003,6 +1105,62 @@ int eik_fim2d_solve(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     return EIK_OK;
 }
 
+int eik_fim2d_solve_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                          const int32_t* map_of, int64_t K, void* stream) {
+    int64_t active = 0;
+    int rc = EIK_OK;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        rc = eik_fim2d_start_seeds(f, d_cost, d_T, seeds, t0, map_of, K, stream);
+        if (rc) return rc;
+        f->defer_sync = f->a.mode == kModePersistent;
+        rc = eik_fim2d_iterate(f, f->max_iters, &active);
+        f->defer_sync = false;
+        if (!rc) rc = finish_solve(f, &active);
+        if (!(rc && f->band_overflow)) break;
+        // a priority band's ring was full: again from the same seeds on the FIFO, as eik_fim2d_solve
+        f->band_overflow = false;
+        f->no_bands = true;
+    }
+    if (rc) return rc;
+    if (active != 0)
+        return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence after %ld iterations (negative costs?)",
+                       (long)f->iterations);
+    return EIK_OK;
+}
+
+// Nearest-seed labels of a converged field (seeds.hip): asynchronous on `stream`, no read-back.
+int eik_labels2d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, const int64_t* seeds,
+                     const double* t0, const int32_t* map_of, int64_t K, int32_t* d_label, void* stream) {
+    if (!c) return EIK_ERR_ARG;
+    const char* who = "eik_labels2d_dev";
+    if (!d_T || !d_label) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_T ? "d_T" : "d_label");
+    if (dtype != EIK_F32 && dtype != EIK_F64) return set_err(c, EIK_ERR_ARG, "%s: bad dtype %d", who, dtype);
+    if (B < 1 || H < 1 || W < 1 || B * H * W >= (1ll << 31))
+        return set_err(c, EIK_ERR_ARG, "%s: B = %ld maps of %ld x %ld (1 .. 2^31 - 1 cells in all)", who, (long)B, (long)H,
+                       (long)W);
+    std::vector<SeedDesc> v;
+    int rc = seeds_check(c, who, B, H, W, dtype == EIK_F64, seeds, t0, map_of, K, v);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = B * H * W;
+    HIPCHK(c, c->lab_work.ensure(sizeof(int) * (size_t)n + sizeof(unsigned) * kLabelPasses));
+    rc = seeds_upload(c, c->lab_seeds, v, st);
+    if (rc) return rc;
+    LabelArgs l{};
+    l.T = d_T;
+    l.H = H;
+    l.W = W;
+    l.n = n;
+    l.seeds = c->lab_seeds.d;
+    l.K = (int)K;
+    l.par = (int*)c->lab_work.p;
+    l.label = d_label;
+    l.flags = (unsigned*)(l.par + n);
+    HIPCHK(c, labels2d(l, dtype == EIK_F64, st));
+    return EIK_OK;
+}
+
 // ---- incremental re-solve after local cost changes (replan.hip)
 // What the update, its restart and adopt apply to: one map, no ghost strips, not a layered block, no
 // live launch, the persistent mode on a raster within its 32-bit offsets.
@@ -1051,6 +1209,9 @@ int eik_fim2d_update(eik_fim2d* f, const int64_t* rects, const int* kinds, int64
     if (rc) return rc;
     if (!f->started || !f->a.cost || !f->a.T)
         return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the solver was never started or adopted");
+    if (f->seeded)  // (the invalidation spares one goal, r.gx / r.gy: the other seeds would be reset)
+        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the bound solve has a seed set (eik_fim2d_start_seeds); start or "
+                                       "adopt a single-goal solve first");
     if (f->a.mode != kModePersistent)
         return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the bound solve did not run in the persistent mode");
     if (f->last_active != 0)
@@ -1150,6 +1311,7 @@ int eik_fim2d_adopt(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     f->rp_timed = false;
     f->rp_fallback = false;
     f->started = true;
+    f->seeded = false;
     f->need_rewind = false;
     f->last_active = 0;
     return EIK_OK;
@@ -1534,6 +1696,9 @@ static int tmap_update_host(eik_ctx* c, const R* cost, R* T, int64_t H, int64_t 
     int rc = get_solver(c, 1, H, W, sizeof(R) == 8 ? EIK_F64 : EIK_F32, &f);
     if (!rc) rc = replan_gate(f, "eik_tmap2d_update");
     if (rc) return rc;
+    if (f->seeded)  // (T is most likely that solve's field, which one goal does not describe)
+        return set_err(c, EIK_ERR_ARG, "eik_tmap2d_update: the bound solve has a seed set (eik_tmap2d_seeds); run a "
+                                       "single-goal solve first");
     HIPCHK(c, c->cost.ensure(sizeof(R) * n));
     HIPCHK(c, c->T.ensure(sizeof(R) * n));
     HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
@@ -1549,7 +1714,48 @@ static int tmap_update_host(eik_ctx* c, const R* cost, R* T, int64_t H, int64_t 
     return EIK_OK;
 }
 
+// one map from a seed set on the cached solver; labels (optional) from the field while it is on the device
+template <typename R>
+static int tmap_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
+                           int64_t K, R* T, int32_t* labels) {
+    if (!c) return EIK_ERR_ARG;
+    if (!cost || !T) return set_err(c, EIK_ERR_ARG, "eik_tmap2d_seeds: %s is NULL", !cost ? "cost" : "T");
+    if (H < 1 || W < 1) return set_err(c, EIK_ERR_ARG, "eik_tmap2d_seeds: bad shape %ld x %ld", (long)H, (long)W);
+    constexpr int dtype = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
+    std::vector<SeedDesc> v;  // (checked before anything is uploaded; the entry points below check again)
+    int rc = seeds_check(c, "eik_tmap2d_seeds", 1, H, W, sizeof(R) == 8, seeds, t0, nullptr, K, v);
+    if (rc) return rc;
+    if (labels && H * W >= (1ll << 31)) return set_err(c, EIK_ERR_ARG, "eik_tmap2d_seeds: labels need fewer than 2^31 cells");
+    const int64_t n = H * W;
+    HIPCHK(c, hipSetDevice(c->device));
+    eik_fim2d* f = nullptr;
+    rc = get_solver(c, 1, H, W, dtype, &f);
+    if (rc) return rc;
+    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
+    HIPCHK(c, c->T.ensure(sizeof(R) * n));
+    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
+    rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = eik_fim2d_solve_seeds(f, c->cost.p, c->T.p, seeds, t0, nullptr, K, c->stream);
+    if (!rc && labels) rc = eik_labels2d_dev(c, c->T.p, dtype, 1, H, W, seeds, t0, nullptr, K, (int32_t*)c->lab_out.p, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
+    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
 extern "C" {
+
+int eik_tmap2d_seeds_f32(eik_ctx* c, const float* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
+                         int64_t K, float* T, int32_t* labels) {
+    return tmap_seeds_host<float>(c, cost, H, W, seeds, t0, K, T, labels);
+}
+
+int eik_tmap2d_seeds_f64(eik_ctx* c, const double* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
+                         int64_t K, double* T, int32_t* labels) {
+    return tmap_seeds_host<double>(c, cost, H, W, seeds, t0, K, T, labels);
+}
 
 int eik_tmap2d_update_f32(eik_ctx* c, const float* cost_new, float* T, int64_t H, int64_t W, int64_t gx, int64_t gy,
                           const int64_t* rects, const int* kinds, int64_t K) {

@@ -422,6 +422,18 @@ __device__ __forceinline__ void activate_goal_sides(const Fim2dArgs& a, int tile
     if (cx == kTile - 1 && tx + 1 < a.ntx) activate(a, tile + 1, 0, 1u, 0.f, kFromW);
 }
 
+// The same for a seed of a seed set with start value `key` >= 0 (seeds.hip): the reasoning holds for
+// every seed that nothing lowers, and the neighbour is keyed by the seed's T0 so that the priority bands
+// order it.
+__device__ __forceinline__ void activate_seed_sides(const Fim2dArgs& a, int tile, int ry, int cx, int th, float key) {
+    const int rem = tile % a.tiles_per_map;
+    const int ty = rem / a.ntx, tx = rem - ty * a.ntx;
+    if (ry == 0 && ty > 0) activate(a, tile - a.ntx, 0, 1u, key, kFromS);
+    if (ry == th - 1 && ty + 1 < a.nty) activate(a, tile + a.ntx, 0, 1u, key, kFromN);
+    if (cx == 0 && tx > 0) activate(a, tile - 1, 0, 1u, key, kFromE);
+    if (cx == kTile - 1 && tx + 1 < a.ntx) activate(a, tile + 1, 0, 1u, key, kFromW);
+}
+
 // Neighbour activations of a write-back with flags f: thread q in 1..4 handles one side (their
 // atomics overlap); thread 0 flags changed subdomain edges for the halo exchange.  (`tid`: the
 // caller's index for this role -- a lane of any one wave may serve, fim2d.hip's follow-through.)

@@ -210,6 +210,12 @@ def lib():
         L.eik_fim2d_update_info.argtypes = [vp, _i64p]
         L.eik_tmap2d_update_f32.argtypes = [vp, _f32p, _f32p, i64, i64, i64, i64, vp, vp, i64]
         L.eik_tmap2d_update_f64.argtypes = [vp, _f64p, _f64p, i64, i64, i64, i64, vp, vp, i64]
+        # multi-source solves: t0 / map_of / labels are nullable host arrays (passed as an address or None)
+        L.eik_fim2d_start_seeds.argtypes = [vp, vp, vp, _i64p, vp, vp, i64, vp]
+        L.eik_fim2d_solve_seeds.argtypes = [vp, vp, vp, _i64p, vp, vp, i64, vp]
+        L.eik_labels2d_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, _i64p, vp, vp, i64, vp, vp]
+        L.eik_tmap2d_seeds_f32.argtypes = [vp, _f32p, i64, i64, _i64p, vp, i64, _f32p, vp]
+        L.eik_tmap2d_seeds_f64.argtypes = [vp, _f64p, i64, i64, _i64p, vp, i64, _f64p, vp]
         _lib = L
         return L
 
@@ -226,6 +232,28 @@ def _rects(rects, kinds):
         if len(k) != len(r):
             raise ValueError(f"{len(r)} rectangles but {len(k)} kinds")
     return r, k, len(r)
+
+
+def _seeds(seeds, t0, map_of=None):
+    """(seeds int64 [K][2], t0 float64 [K] or None, map_of int32 [K] or None, K) as host arrays for the
+    multi-source entry points"""
+    s = np.ascontiguousarray(seeds, dtype=np.int64).reshape(-1, 2)
+    K = len(s)
+    t = None
+    if t0 is not None:
+        t = np.ascontiguousarray(t0, dtype=np.float64).reshape(-1)
+        if len(t) != K:
+            raise ValueError(f"{K} seeds but {len(t)} start values")
+    m = None
+    if map_of is not None:
+        m = np.ascontiguousarray(map_of, dtype=np.int32).reshape(-1)
+        if len(m) != K:
+            raise ValueError(f"{K} seeds but {len(m)} map_of entries")
+    return s, t, m, K
+
+
+def _addr(a):
+    return None if a is None else a.ctypes.data
 
 
 EXPORTED = [
@@ -246,6 +274,8 @@ EXPORTED = [
     "eik_plan2d_batch_f32",
     "eik_fim2d_update", "eik_fim2d_resolve", "eik_fim2d_adopt", "eik_fim2d_update_info",
     "eik_tmap2d_update_f32", "eik_tmap2d_update_f64",
+    "eik_fim2d_start_seeds", "eik_fim2d_solve_seeds", "eik_labels2d_dev", "eik_tmap2d_seeds_f32",
+    "eik_tmap2d_seeds_f64",
 ]
 
 
@@ -372,6 +402,43 @@ class Context:
         self._chk(fn(self._h, cost, out, H, W, int(goal[0]), int(goal[1]), r.ctypes.data if K else None,
                      k.ctypes.data if k is not None and K else None, K))
         return out
+
+    def tmap2d_seeds(self, cost, seeds, t0=None, dtype=np.float64, labels=False):
+        """The field of a seed set (eik_tmap2d_seeds_*): seeds K x (x, y), t0 their start values (None: all
+        0) -> T, or (T, labels int32: the seed each cell belongs to, -1 = none) with labels=True."""
+        cost = np.ascontiguousarray(cost, dtype=dtype)
+        H, W = cost.shape
+        s, t, _, K = _seeds(seeds, t0)
+        T = result_empty(cost.shape, cost.dtype)
+        lab = np.empty(cost.shape, np.int32) if labels else None
+        fn = lib().eik_tmap2d_seeds_f64 if cost.dtype == np.float64 else lib().eik_tmap2d_seeds_f32
+        self._chk(fn(self._h, cost, H, W, s, _addr(t), K, T, _addr(lab)))
+        return (T, lab) if labels else T
+
+    def labels2d(self, T, seeds, t0=None, map_of=None):
+        """Nearest-seed labels (eik_labels2d_dev) of a converged field T -- H x W or a stack B x H x W,
+        float32 or float64, a numpy array (uploaded through torch) or a torch tensor on this context's
+        device -- for the seed list that produced it -> int32 labels of T's shape, of T's kind."""
+        import torch
+
+        host = not isinstance(T, torch.Tensor)
+        if host:
+            T = np.asarray(T)
+            T = np.ascontiguousarray(T, dtype=np.float32 if T.dtype == np.float32 else np.float64)
+            Td = torch.from_numpy(T).to(torch.device("cuda", self.device))
+        else:
+            Td = T.contiguous()
+        if Td.dtype not in (torch.float32, torch.float64) or Td.dim() not in (2, 3):
+            raise ValueError("labels2d: T must be a float32 / float64 field H x W or a stack B x H x W")
+        B = 1 if Td.dim() == 2 else Td.shape[0]
+        H, W = Td.shape[-2:]
+        s, t, m, K = _seeds(seeds, t0, map_of)
+        lab = torch.empty(Td.shape, dtype=torch.int32, device=Td.device)
+        stream = torch.cuda.current_stream(Td.device).cuda_stream
+        self._chk(lib().eik_labels2d_dev(self._h, Td.data_ptr(), EIK_F64 if Td.dtype == torch.float64 else EIK_F32,
+                                         B, H, W, s, _addr(t), _addr(m), K, lab.data_ptr(), stream))
+        torch.cuda.current_stream(Td.device).synchronize()
+        return lab.cpu().numpy() if host else lab
 
     def tmap2d_batch(self, costs, goals):
         costs = np.ascontiguousarray(costs, dtype=np.float32)
@@ -668,6 +735,16 @@ class Fim2d:
     def solve(self, d_cost, d_T, goals, stream=None):
         self.ctx._chk(lib().eik_fim2d_solve(self._h, d_cost, d_T, np.ascontiguousarray(goals, np.int64).reshape(-1),
                                             stream))
+
+    # multi-source solves (eik_fim2d_start_seeds / solve_seeds): seeds K x (x, y), t0 None = all 0,
+    # map_of None needs B == 1
+    def start_seeds(self, d_cost, d_T, seeds, t0=None, map_of=None, stream=None):
+        s, t, m, K = _seeds(seeds, t0, map_of)
+        self.ctx._chk(lib().eik_fim2d_start_seeds(self._h, d_cost, d_T, s, _addr(t), _addr(m), K, stream))
+
+    def solve_seeds(self, d_cost, d_T, seeds, t0=None, map_of=None, stream=None):
+        s, t, m, K = _seeds(seeds, t0, map_of)
+        self.ctx._chk(lib().eik_fim2d_solve_seeds(self._h, d_cost, d_T, s, _addr(t), _addr(m), K, stream))
 
     def pack_edges(self, n, s, w, e):
         self.ctx._chk(lib().eik_fim2d_pack_edges(self._h, n, s, w, e))
