@@ -519,6 +519,11 @@ int eik_costmap_f64(eik_ctx* ctx, const double* Z, int64_t H, int64_t W, double 
 /* the same on device buffers, async on `stream` except the two hole-filling solves */
 int eik_costmap_dev(eik_ctx* ctx, const double* d_Z, int64_t H, int64_t W, double resolution, double size,
                     const eik_costmap_params* params, double* d_cost, uint8_t* d_obst, void* stream);
+/* The cost tail alone (:1180-1216; the code eik_costmap_* runs for it): obst is the H x W 0/1 obstacle
+ * mask as it stands after :1177, H, W >= 3, resolution > 0.  cost_out [y][x] and obst_out (nullable)
+ * as eik_costmap_f64 returns them. */
+int eik_cost_tail_u8(eik_ctx* ctx, const uint8_t* obst, int64_t H, int64_t W, double resolution,
+                     const eik_costmap_params* params, double* cost_out, uint8_t* obst_out);
 /* surface_normal(resolution, size, z) :37-80 -> unit normals (H x W each) */
 int eik_surface_normal_f64(eik_ctx* ctx, const double* Z, int64_t H, int64_t W, double size, double* Nx, double* Ny,
                            double* Nz);

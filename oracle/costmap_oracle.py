@@ -145,16 +145,17 @@ def obstacle_morphology(obst, resolution, diagonal=0.9):
     return erode(obst, se)
 
 
-def cost_tail(obst, resolution, expansion=1.0, gradient=10.0, dilated=None):
+def cost_tail(obst, resolution, expansion=1.0, gradient=10.0, dilated=None, high=300.0):
     """:1180-1216 on the uint8 obstacle map after :1177 -> (cMap [x, y], obstMap float64 [y, x]).
-    `dilated` (tests): :1192's cv2.dilate result, else restated here."""
+    `dilated` (tests): :1192's cv2.dilate result, else restated here.  `high`: :1187's obstacle cost
+    (the blur's fill value, :1210, stays the literal 300)."""
     obst = np.array(obst, dtype=np.uint8)
     obst[0, :] = 1  # :1180-1183
     obst[-1, :] = 1
     obst[:, 0] = 1
     obst[:, -1] = 1
     obst = np.float64(obst)  # :1184
-    high = obst * 300  # :1187
+    highmap = obst * high  # :1187
     se = structural_disk(int(round(expansion / resolution)))  # :1190-1192
     dil = dilate(obst, se) if dilated is None else dilated
     dist = resolution * ndimage.distance_transform_edt(obst == 0)  # :1194
@@ -162,7 +163,7 @@ def cost_tail(obst, resolution, expansion=1.0, gradient=10.0, dilated=None):
     pos = od > 0
     if np.any(pos):
         od[pos] = od[pos] - np.min(od[pos])  # :1197-1198
-    cmap = 1 + (high + od * gradient).T  # :1200-1205
+    cmap = 1 + (highmap + od * gradient).T  # :1200-1205
     h = np.ones((50, 50)) / 50 ** 2  # :1208-1210
     cmap = signal.convolve2d(cmap, np.flipud(h), mode="same", fillvalue=300)
     cmap[0, :] = np.inf  # :1213-1216
@@ -172,7 +173,7 @@ def cost_tail(obst, resolution, expansion=1.0, gradient=10.0, dilated=None):
     return cmap, obst
 
 
-def cost_map(Zs, resolution, size, slope_max=0.20, diagonal=0.9, expansion=1.0, gradient=10.0):
+def cost_map(Zs, resolution, size, slope_max=0.20, diagonal=0.9, expansion=1.0, gradient=10.0, high=300.0):
     """The cost raster of main() (Coupled_motion_planner.py:1101-1216) from the DEM Zs
     (loaded at :1098-1099).  Returns (cMap, obstMap): cMap exactly as the reference holds it
     before calling FM.biComputeTmap(cMap.T, ...) (i.e. indexed [x, y]), obstMap [y, x] float64.
@@ -180,4 +181,4 @@ def cost_map(Zs, resolution, size, slope_max=0.20, diagonal=0.9, expansion=1.0, 
     (tests/golden/costmap.npz, tests/test_costmap_golden.py); the cv2 middle to brute force."""
     obst = obstacle_head(Zs, resolution, size, slope_max)
     obst = obstacle_morphology(obst, resolution, diagonal)
-    return cost_tail(obst, resolution, expansion, gradient)
+    return cost_tail(obst, resolution, expansion, gradient, high=high)

@@ -2844,54 +2844,77 @@ static int cm_fill(eik_ctx* c, unsigned char* m, int64_t H, int64_t W, float* fc
     return EIK_OK;
 }
 
+// The builder's scratch: 3 masks, 3 int planes (column distances, squared EDT, envelope apexes),
+// 2 f32 (fill cost, fill T), 2 f64 planes, reduction words.  obst = the caller's device mask if given.
+struct cm_scratch {
+    unsigned char *obst, *tmp, *dil;
+    int *g, *D, *vbuf;
+    float *fcost, *fT;
+    double *work, *tmpd;
+    unsigned long long* red;
+};
+
+static int cm_scratch_get(eik_ctx* c, int64_t n, uint8_t* d_obst, cm_scratch* s) {
+    HIPCHK(c, c->cm_u8.ensure(3 * n + 64));
+    HIPCHK(c, c->cm_i32.ensure(sizeof(int) * 3 * n));
+    HIPCHK(c, c->cm_f32.ensure(sizeof(float) * 2 * n));
+    HIPCHK(c, c->cm_f64.ensure(sizeof(double) * 2 * n + 64));
+    s->obst = d_obst ? d_obst : (unsigned char*)c->cm_u8.p;
+    s->tmp = (unsigned char*)c->cm_u8.p + n;
+    s->dil = (unsigned char*)c->cm_u8.p + 2 * n;
+    s->g = (int*)c->cm_i32.p;
+    s->D = s->g + n;
+    s->vbuf = s->g + 2 * n;
+    s->fcost = (float*)c->cm_f32.p;
+    s->fT = s->fcost + n;
+    s->work = (double*)c->cm_f64.p;
+    s->tmpd = s->work + n;
+    s->red = (unsigned long long*)(s->tmpd + n);
+    return EIK_OK;
+}
+
+static const eik_costmap_params kCmDefaults = {0.20, 0.9, 1.0, 10.0, 300.0};
+
+// The cost tail (:1180-1216) on the device mask s.obst as it stands after :1177: obstacle border,
+// expansion dilation, distance ramp, cost, blur.  s.obst ends as the final obstacle map.
+static int cm_tail(eik_ctx* c, const cm_scratch& s, int64_t H, int64_t W, double res, const eik_costmap_params& p,
+                   double* d_cost, hipStream_t st) {
+    const int r3 = (int)std::nearbyint(p.expansion / res);                      // :1190-1191
+    HIPCHK(c, cm_border(s.obst, H, W, 1, st));                                  // :1180-1184
+    HIPCHK(c, cm_morph(s.obst, H, W, r3, false, s.dil, s.g, s.D, s.vbuf, st));  // :1192
+    HIPCHK(c, cm_edt_ramp(s.obst, H, W, r3, s.g, s.D, s.vbuf, st));  // :1194 (distance to obstacles, as :1196 uses it)
+    HIPCHK(c, cm_cost(s.obst, s.dil, s.D, H, W, res, p.high, p.gradient, s.work, s.tmpd, d_cost, s.red, st));  // :1187-1216
+    return EIK_OK;
+}
+
 extern "C" {
 
 int eik_costmap_dev(eik_ctx* c, const double* d_Z, int64_t H, int64_t W, double res, double size,
                     const eik_costmap_params* params, double* d_cost, uint8_t* d_obst, void* stream) {
     if (!c || !d_Z || !d_cost || H < 3 || W < 3 || !(res > 0) || !(size > 0))
         return c ? set_err(c, EIK_ERR_ARG, "bad cost-map arguments") : EIK_ERR_ARG;
-    const eik_costmap_params p = params ? *params : eik_costmap_params{0.20, 0.9, 1.0, 10.0, 300.0};
+    const eik_costmap_params p = params ? *params : kCmDefaults;
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = (hipStream_t)stream;
-    const int64_t n = H * W;
-    // scratch: 3 masks, 3 int planes (column distances, squared EDT, envelope apexes), 2 f32 (fill
-    // cost, fill T), 2 f64 planes, reduction words
-    HIPCHK(c, c->cm_u8.ensure(3 * n + 64));
-    HIPCHK(c, c->cm_i32.ensure(sizeof(int) * 3 * n));
-    HIPCHK(c, c->cm_f32.ensure(sizeof(float) * 2 * n));
-    HIPCHK(c, c->cm_f64.ensure(sizeof(double) * 2 * n + 64));
-    unsigned char* obst = d_obst ? d_obst : (unsigned char*)c->cm_u8.p;
-    unsigned char* tmp = (unsigned char*)c->cm_u8.p + n;
-    unsigned char* dil = (unsigned char*)c->cm_u8.p + 2 * n;
-    int* g = (int*)c->cm_i32.p;
-    int* D = g + n;
-    int* vbuf = g + 2 * n;
-    float* fcost = (float*)c->cm_f32.p;
-    float* fT = fcost + n;
-    double* work = (double*)c->cm_f64.p;
-    double* tmpd = work + n;
-    unsigned long long* red = (unsigned long long*)(tmpd + n);
+    cm_scratch s;
+    int rc = cm_scratch_get(c, H * W, d_obst, &s);
+    if (rc) return rc;
     const int r1 = 10;                                              // :1167
     const int r2 = (int)std::nearbyint((p.diagonal / 2) / res);     // :1172-1173
-    const int r3 = (int)std::nearbyint(p.expansion / res);          // :1190-1191
-    HIPCHK(c, cm_normals(d_Z, H, W, size, red, p.slope_max, obst, nullptr, nullptr, nullptr, st));  // :1104-1160
+    HIPCHK(c, cm_normals(d_Z, H, W, size, s.red, p.slope_max, s.obst, nullptr, nullptr, nullptr, st));  // :1104-1160
     // min(Z)'s key (red is reused below) for the rover path's z lookup (:1101, :1246): misc word 5
     HIPCHK(c, c->misc.ensure(64));
-    HIPCHK(c, hipMemcpyAsync((unsigned long long*)c->misc.p + 5, red, sizeof(unsigned long long),
+    HIPCHK(c, hipMemcpyAsync((unsigned long long*)c->misc.p + 5, s.red, sizeof(unsigned long long),
                              hipMemcpyDeviceToDevice, st));
-    int rc = cm_fill(c, obst, H, W, fcost, fT, st);                 // :1163-1164
+    rc = cm_fill(c, s.obst, H, W, s.fcost, s.fT, st);                         // :1163-1164
     if (rc) return rc;
-    HIPCHK(c, cm_morph(obst, H, W, r1, true, tmp, g, D, vbuf, st));  // :1168
-    HIPCHK(c, cm_morph(tmp, H, W, r1, false, obst, g, D, vbuf, st)); // :1169
-    HIPCHK(c, cm_morph(obst, H, W, r2, false, tmp, g, D, vbuf, st)); // :1175
-    rc = cm_fill(c, tmp, H, W, fcost, fT, st);                      // :1176
+    HIPCHK(c, cm_morph(s.obst, H, W, r1, true, s.tmp, s.g, s.D, s.vbuf, st));  // :1168
+    HIPCHK(c, cm_morph(s.tmp, H, W, r1, false, s.obst, s.g, s.D, s.vbuf, st)); // :1169
+    HIPCHK(c, cm_morph(s.obst, H, W, r2, false, s.tmp, s.g, s.D, s.vbuf, st)); // :1175
+    rc = cm_fill(c, s.tmp, H, W, s.fcost, s.fT, st);                          // :1176
     if (rc) return rc;
-    HIPCHK(c, cm_morph(tmp, H, W, r2, true, obst, g, D, vbuf, st));  // :1177
-    HIPCHK(c, cm_border(obst, H, W, 1, st));                         // :1180-1184
-    HIPCHK(c, cm_morph(obst, H, W, r3, false, dil, g, D, vbuf, st)); // :1192
-    HIPCHK(c, cm_edt_ramp(obst, H, W, r3, g, D, vbuf, st));          // :1194 (distance to obstacles, as :1196 uses it)
-    HIPCHK(c, cm_cost(obst, dil, D, H, W, res, p.high, p.gradient, work, tmpd, d_cost, red, st));  // :1187-1216
-    return EIK_OK;
+    HIPCHK(c, cm_morph(s.tmp, H, W, r2, true, s.obst, s.g, s.D, s.vbuf, st));  // :1177
+    return cm_tail(c, s, H, W, res, p, d_cost, st);                           // :1180-1216
 }
 
 int eik_costmap_f64(eik_ctx* c, const double* Z, int64_t H, int64_t W, double res, double size,
@@ -2908,6 +2931,27 @@ int eik_costmap_f64(eik_ctx* c, const double* Z, int64_t H, int64_t W, double re
     if (rc) return rc;
     HIPCHK(c, dev_to_host(c, cost_out, dC, sizeof(double) * n, c->stream));
     if (obst_out) HIPCHK(c, dev_to_host(c, obst_out, dO, n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
+int eik_cost_tail_u8(eik_ctx* c, const uint8_t* obst, int64_t H, int64_t W, double res,
+                     const eik_costmap_params* params, double* cost_out, uint8_t* obst_out) {
+    if (!c || !obst || !cost_out || H < 3 || W < 3 || !(res > 0))
+        return c ? set_err(c, EIK_ERR_ARG, "bad cost-tail arguments") : EIK_ERR_ARG;
+    const eik_costmap_params p = params ? *params : kCmDefaults;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = H * W;
+    cm_scratch s;
+    int rc = cm_scratch_get(c, n, nullptr, &s);
+    if (rc) return rc;
+    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
+    double* dC = (double*)c->T2.p;
+    HIPCHK(c, host_to_dev(c, s.obst, obst, n, c->stream));
+    rc = cm_tail(c, s, H, W, res, p, dC, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, dev_to_host(c, cost_out, dC, sizeof(double) * n, c->stream));
+    if (obst_out) HIPCHK(c, dev_to_host(c, obst_out, s.obst, n, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return EIK_OK;
 }

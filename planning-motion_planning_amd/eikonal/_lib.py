@@ -160,6 +160,7 @@ def lib():
         L.eik_path3d_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, _f64p, _f64p, C.c_double, vp, i64, vp, vp, vp]
         L.eik_costmap_f64.argtypes = [vp, _f64p, i64, i64, C.c_double, C.c_double, P(CostmapParams), _f64p, vp]
         L.eik_costmap_dev.argtypes = [vp, vp, i64, i64, C.c_double, C.c_double, P(CostmapParams), vp, vp, vp]
+        L.eik_cost_tail_u8.argtypes = [vp, _u8p, i64, i64, C.c_double, P(CostmapParams), _f64p, vp]
         L.eik_surface_normal_f64.argtypes = [vp, _f64p, i64, i64, C.c_double, _f64p, _f64p, _f64p]
         L.eik_image_fill_u8.argtypes = [vp, _u8p, i64, i64, _u8p]
         L.eik_disk_morph_u8.argtypes = [vp, _u8p, i64, i64, C.c_int, C.c_int, _u8p]
@@ -263,7 +264,7 @@ EXPORTED = [
     "eik_fim2d_iterate", "eik_fim2d_solve", "eik_fim2d_pack_edges", "eik_fim2d_merge_ghost", "eik_fim2d_active",
     "eik_fim2d_stats", "eik_path2d_dev", "eik_selftest_walker_math", "eik_tmap3d_f32", "eik_tmap3d_f64",
     "eik_tmap3d_early_f32", "eik_tmap3d_early_f64", "eik_fim3d_early_exit", "eik_path3d_f64", "eik_fim3d_solve",
-    "eik_path3d_dev", "eik_costmap_f64", "eik_costmap_dev", "eik_surface_normal_f64", "eik_image_fill_u8", "eik_disk_morph_u8",
+    "eik_path3d_dev", "eik_costmap_f64", "eik_costmap_dev", "eik_cost_tail_u8", "eik_surface_normal_f64", "eik_image_fill_u8", "eik_disk_morph_u8",
     "eik_load_dem_txt", "eik_io_last_error", "eik_fim2d_live_bind", "eik_fim2d_launch", "eik_fim2d_live_pack",
     "eik_fim2d_live_merge", "eik_fim2d_release", "eik_node_allreduce", "eik_node_shm_open",
     "eik_node_shm_close", "eik_node_shm_unlink", "eik_ipc_alloc", "eik_ipc_free", "eik_ipc_open", "eik_ipc_close",
@@ -603,6 +604,17 @@ class Context:
         p = C.byref(params) if params is not None else None
         self._chk(lib().eik_costmap_f64(self._h, Z, H, W, float(resolution), float(size), p, cost, obst.ctypes.data))
         return cost, obst
+
+    def cost_tail(self, obst, resolution, params=None):
+        """Coupled_motion_planner.py:1180-1216 alone (eik_cost_tail_u8), on the 0/1 uint8 obstacle mask as
+        it stands after :1177: (cost [y][x], final obstacle map [y][x] uint8), as costmap() returns them."""
+        obst = np.ascontiguousarray(obst, dtype=np.uint8)
+        H, W = obst.shape
+        cost = np.empty((H, W), np.float64)
+        out = np.empty((H, W), np.uint8)
+        p = C.byref(params) if params is not None else None
+        self._chk(lib().eik_cost_tail_u8(self._h, obst, H, W, float(resolution), p, cost, out.ctypes.data))
+        return cost, out
 
     def rover_path(self, Z, query, params=None, want_cost=False):
         """Planner step 1 on the GPU (Coupled_motion_planner.py:1097-1258): DEM -> (roverPath (N, 3),

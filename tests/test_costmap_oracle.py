@@ -59,6 +59,23 @@ def test_fill_vs_brute(seed):
     assert np.array_equal(CO.image_filling(im), brute_fill(im))
 
 
+@pytest.mark.parametrize("shape,r", [((70, 90), 7), ((40, 33), 20), ((5, 64), 3)])
+@pytest.mark.parametrize("erode", [False, True])
+def test_stamp_morph_vs_oracle(shape, r, erode):
+    """tests/morph_stamp.py (the reference of the radius-251 GPU cases) bit-exact against the oracle's
+    shifts: dilation of a sparse mask (density 0.02), erosion of a dense one (0.97)."""
+    import morph_stamp
+
+    rng = np.random.default_rng(100 + r + erode)
+    im = (rng.random(shape) < (0.97 if erode else 0.02)).astype(np.uint8)
+    assert 0 < im.sum() < im.size
+    se = CO.structural_disk(r)
+    if erode:
+        assert np.array_equal(morph_stamp.erode(im, r), CO.erode(im, se))
+    else:
+        assert np.array_equal(morph_stamp.dilate(im, r), CO.dilate(im, se))
+
+
 def test_disk():
     d = CO.structural_disk(3)
     yy, xx = np.mgrid[-3:4, -3:4]
