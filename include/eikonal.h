@@ -47,7 +47,9 @@ typedef enum {
     EIK_PATH_DONE = 0,     /* stop radius (< 1.5 cells) or step budget hit; end appended (:231-234) */
     EIK_PATH_FALLBACK = 1, /* NaN gradient: the reference's fallback returns a truncated path
                               (numpy-2 behaviour of FastMarching.py:178-218)                       */
-    EIK_PATH_ERROR = 2     /* the reference raises out of getPathGDM (NaN point / out of range)     */
+    EIK_PATH_ERROR = 2,    /* the reference raises out of getPathGDM (NaN point / out of range)     */
+    EIK_PATH_STUCK = 3     /* eik_path2d_safe_* only: no lower neighbour to descend to, or the
+                              iteration budget ran out short of the stop radius; end NOT appended   */
 } eik_path_status;
 
 typedef struct eik_ctx eik_ctx;
@@ -463,6 +465,46 @@ int eik_path2d_batch_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t B, in
 int eik_path2d_batch_f64(eik_ctx* ctx, const double* T, int64_t B, int64_t H, int64_t W, int64_t P,
                          const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
                          int64_t cap, int64_t* n_out, int* status);
+
+/* ---- obstacle-safe 2D paths (no reference counterpart beyond the cited lines) ---------------
+ * getPathGDM stops at, tunnels through or stalls beside +inf cells (it is the reference's walk,
+ * kept bit for bit above).  These entries walk the same field by a rule that does not:
+ *   G' = computeGradient's (Gnx, Gny) with NaN at every node whose T is +inf.  Per iteration
+ *   (round(15000 / tau) of them), p the last point:
+ *     - the reference's step (:175-176, :220-230, the default walker's bits) unless the
+ *       interpolation of G' at p is NaN or the walk is in integer mode;
+ *     - else the fallback of :178-218 as intended (FastMarching3D.py:212-264): n = rint(p), half to
+ *       even; while T[n] is +inf drop the last point and take n from the one before (none left:
+ *       EIK_PATH_ERROR); drop the points closer than 1 to n; append n; append the 4-neighbour of n
+ *       with the smallest T strictly below T[n] (scanned y-1, y+1, x-1, x+1, the first wins ties;
+ *       none: EIK_PATH_STUCK);
+ *     - stop within 1.5 of end (EIK_PATH_DONE, end appended);
+ *     - stall rule: when T at the nearest node of the new point has not fallen below its running
+ *       minimum for S = max(16, ceil(8 / tau)) iterations in a row, every later iteration takes
+ *       the fallback (integer mode).
+ *   A NaN point, a negative coordinate or an interpolation cell outside the raster is
+ *   EIK_PATH_ERROR; a budget that runs out short of the stop radius is EIK_PATH_STUCK (rows: ERROR).
+ *   Rows grow by at most one per iteration, so cap is the default walker's.
+ * Guarantee: with tau <= 0.5, a converged field and finite T[init], the status is DONE or STUCK by
+ * budget, and no emitted point has a +inf node as its nearest node.  Segments between points are
+ * NOT swept: a step may pass the gap between two impassable cells that touch only at a corner.
+ * The path equals getPathGDM's up to the first blocked step or stall and differs only from there on.
+ * tau: 0 < tau <= 1 (a step longer than a cell cannot be made safe by sampling points), else
+ * EIK_ERR_ARG, as everything eik_path2d_dev / eik_path2d_batch_dev check.
+ * info (nullable; int64[4] per path): fallbacks taken, points dropped, the first iteration run in
+ * integer mode (-1: never), iterations run.  Layout, staging and rounds as the entries above. */
+int eik_path2d_safe_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t H, int64_t W, const double init[2],
+                        const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
+                        int64_t* d_info, void* stream);
+int eik_path2d_safe_f64(eik_ctx* ctx, const double* T, int64_t H, int64_t W, const double init[2], const double end[2],
+                        double tau, double* out, int64_t cap, int64_t* n_out, int* status, int64_t info[4]);
+int eik_path2d_safe_batch_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
+                              const int32_t* map_of, const double* inits, const double* ends, double tau,
+                              double* d_out, int64_t cap, int64_t* d_n_out, int* d_status, int64_t* d_info,
+                              void* stream);
+int eik_path2d_safe_batch_f64(eik_ctx* ctx, const double* T, int64_t B, int64_t H, int64_t W, int64_t P,
+                              const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
+                              int64_t cap, int64_t* n_out, int* status, int64_t* info);
 
 /* FastMarching3D.getPathGDM, batched as above: d_T [B][H][W][L]; inits, ends: P x 3 (x, y, z);
  * d_out: P x cap x 3.  Every path is bit-identical to eik_path3d_dev.  EIK_ERR_ARG as above, with

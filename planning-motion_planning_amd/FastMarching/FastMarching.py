@@ -12,7 +12,13 @@ Additions with no reference counterpart:
   getPathsGDM(T, inits, end, tau)        many getPathGDM walks on one field in one GPU launch
   updateTmap(costMap, Tmap, goal, changed)  computeTmap's field after local cost changes, from the old field
   computeTmapMulti(costMap, goals, offsets, labels)  the field of a goal set with start values (+ nearest-goal labels)
-  getPathsToNearest(T, labels, goals, inits, tau)    each start's path to the goal its cell belongs to, one launch
+  getPathsToNearest(T, labels, goals, inits, tau, safe=False)  each start's path to the goal its cell belongs to, one launch
+  getPathSafe(T, init, end, tau)         the obstacle-safe walk: a step blocked by a +inf cell or a stalled walk
+                                         descends node to node instead; 0 < tau <= 1
+  getPathsSafe(T, inits, end, tau)       many getPathSafe walks on one field in one GPU launch
+
+getPathGDM, getPathsGDM and getPathsToNearest's default keep the reference's behaviour beside +inf cells,
+the truncated path of its NaN fallback included; the safe walks are a mode of their own.
 
 Scalar/list helpers that the reference exposes at module level keep their reference
 semantics on the host (they operate on Python scalars and lists the caller owns):
@@ -36,7 +42,7 @@ import os
 
 import numpy as np
 
-from eikonal import default_context, PATH_ERROR
+from eikonal import default_context, PATH_ERROR, PATH_STUCK
 from eikonal._lib import OPT_EXACT_BAND
 
 _DTYPE = np.float32 if os.environ.get("EIKONAL_DTYPE", "float64") in ("float32", "f32") else np.float64
@@ -228,6 +234,43 @@ def getPathsGDM(totalCostMap, initWaypoints, endWaypoint, tau):
     return [path for path, _ in res]
 
 
+def _safe_paths(who, res):
+    """the paths of Context.path2d_safe* results; IndexError / RuntimeError naming the first bad path"""
+    for p, (path, status, _) in enumerate(res):
+        if status == PATH_ERROR:
+            raise IndexError(f"{who}: the descent of path {p} left the field or started on an impassable cell")
+        if status == PATH_STUCK:
+            last = tuple(int(round(v)) for v in path[-1])
+            raise RuntimeError(f"{who}: path {p} is stuck at node {last}: no lower neighbour, or out of iterations")
+    return [path for path, _, _ in res]
+
+
+def getPathSafe(totalCostMap, initWaypoint, endWaypoint, tau):
+    """No reference counterpart: getPathGDM's walk made safe beside +inf cells -> (K, 2)
+    float64 path from init to end.  A step whose interpolation would use an impassable node, and a walk
+    whose arrival time stops falling, descend node to node instead; no returned point lies nearest an
+    impassable node (tau <= 0.5, converged field).  Equal to getPathGDM's path up to the first such step.
+    0 < tau <= 1 (ValueError).  RuntimeError: stuck (names the last node); IndexError as getPathGDM."""
+    if not 0 < tau <= 1:
+        raise ValueError(f"getPathSafe: tau = {tau} (0 < tau <= 1 needed)")
+    init = np.asarray(initWaypoint, dtype=np.float64).reshape(-1)[:2]
+    end = np.asarray(endWaypoint, dtype=np.float64).reshape(-1)[:2]
+    res = _ctx().path2d_safe(np.ascontiguousarray(totalCostMap, dtype=np.float64), init, end, float(tau))
+    return _safe_paths("getPathSafe", [res])[0]
+
+
+def getPathsSafe(totalCostMap, initWaypoints, endWaypoint, tau):
+    """No reference counterpart: getPathSafe from every row of initWaypoints (P, 2) to endWaypoint on one
+    field, in one launch -> a list of P (K, 2) float64 paths, each equal to getPathSafe's for that start."""
+    if not 0 < tau <= 1:
+        raise ValueError(f"getPathsSafe: tau = {tau} (0 < tau <= 1 needed)")
+    inits = np.asarray(initWaypoints, dtype=np.float64)
+    inits = inits.reshape(-1, inits.shape[-1])[:, :2]
+    end = np.asarray(endWaypoint, dtype=np.float64).reshape(-1)[:2]
+    res = _ctx().path2d_safe_batch(np.ascontiguousarray(totalCostMap, dtype=np.float64), inits, end, float(tau))
+    return _safe_paths("getPathsSafe", res)
+
+
 def _goal_list(goals, shape):
     """goals as a (K, 2) int64 array of nodes (x, y): a list of nodes, or a boolean mask of `shape` whose
     True cells are the seeds in row-major order"""
@@ -258,11 +301,12 @@ def computeTmapMulti(costMap, goals, offsets=None, labels=False):
     return res.astype(np.float64, copy=False)
 
 
-def getPathsToNearest(totalCostMap, labels, goals, initWaypoints, tau):
+def getPathsToNearest(totalCostMap, labels, goals, initWaypoints, tau, safe=False):
     """No reference counterpart: from every row of initWaypoints (P, 2), getPathGDM to the goal its cell
     belongs to -- goals[labels[node(start)]], with (totalCostMap, labels) from computeTmapMulti(...,
     labels=True) and the same goals -- in one launch -> a list of P (K, 2) float64 paths.  ValueError
-    names a start whose cell has no label (-1: unreached); IndexError as getPathsGDM."""
+    names a start whose cell has no label (-1: unreached); IndexError as getPathsGDM.  safe=True walks
+    as getPathSafe does (0 < tau <= 1; RuntimeError names a stuck path) instead of as getPathGDM."""
     T = np.ascontiguousarray(totalCostMap, dtype=np.float64)
     lab = np.asarray(labels)
     if lab.shape != T.shape:
@@ -277,6 +321,10 @@ def getPathsToNearest(totalCostMap, labels, goals, initWaypoints, tau):
         if k < 0 or k >= len(g):
             raise ValueError(f"getPathsToNearest: start {p} ({x}, {y}) belongs to no goal (label {k})")
         ends[p] = g[k]
+    if safe:
+        if not 0 < tau <= 1:
+            raise ValueError(f"getPathsToNearest: tau = {tau} (0 < tau <= 1 needed with safe=True)")
+        return _safe_paths("getPathsToNearest", _ctx().path2d_safe_batch(T, inits, ends, float(tau)))
     res = _ctx().path2d_batch(T, inits, ends, float(tau))
     bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
     if bad:

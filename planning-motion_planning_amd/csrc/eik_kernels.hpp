@@ -268,6 +268,21 @@ struct GdmBatchArgs {
 hipError_t gdm2d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st);
 hipError_t gdm3d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st);
 
+// The obstacle-safe 2D walker (gdm_safe.hip): the walk's arguments as the default
+// walker's (`fused` unused), the stall rule's S and the per-path info words.
+struct GdmSafeArgs {
+    Gdm2dArgs a;
+    long stall;            // S = max(16, ceil(8 / tau))
+    int64_t* info;         // [4] fallbacks, points dropped, first integer-mode iteration (-1), iterations; or null
+};
+struct GdmSafeBatchArgs {
+    GdmBatchArgs b;
+    long stall;
+    int64_t* info;         // [P][4], or null
+};
+hipError_t gdm2d_safe(const GdmSafeArgs& a, bool f64, hipStream_t st);
+hipError_t gdm2d_safe_batch(const GdmSafeBatchArgs& a, bool f64, hipStream_t st);
+
 // Cost-raster builder (costmap.hip), f64 DEM -> f64 cost, uint8 obstacle masks.
 hipError_t cm_normals(const double* Z, int64_t H, int64_t W, double size, unsigned long long* zmin, double slope_max,
                       unsigned char* obst, double* Nx, double* Ny, double* Nz, hipStream_t st);

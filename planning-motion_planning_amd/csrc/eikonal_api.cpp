@@ -2241,6 +2241,111 @@ int eik_path2d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int6
     return batch_fetch(c, 2, P, cap, d_out, d_n, d_st, out, n_out, status);
 }
 
+// ---- the obstacle-safe 2D walker (gdm_safe.hip): the entries above with tau <= 1 and the info words
+static long safe_stall(double tau) { return std::max(16L, (long)std::ceil(8.0 / tau)); }  // S of the stall rule
+
+int eik_path2d_safe_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, const double init[2],
+                        const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
+                        int64_t* d_info, void* stream) {
+    if (!c || !d_T || !init || !end || !d_out || !d_n_out || !d_status || cap < 2 || H < 3 || W < 3 || !(tau > 0))
+        return c ? set_err(c, EIK_ERR_ARG, "bad path arguments") : EIK_ERR_ARG;
+    if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
+    GdmSafeArgs s;
+    Gdm2dArgs& a = s.a;
+    a.T = d_T;
+    a.H = H;
+    a.W = W;
+    a.ix = init[0];
+    a.iy = init[1];
+    a.ex = end[0];
+    a.ey = end[1];
+    a.tau = tau;
+    a.steps = (long)std::nearbyint(15000.0 / tau);  // round(15000/tau), FastMarching.py:173
+    a.out = d_out;
+    a.cap = cap;
+    a.n_out = d_n_out;
+    a.status = d_status;
+    a.fused = 0;
+    s.stall = safe_stall(tau);
+    s.info = d_info;
+    HIPCHK(c, gdm2d_safe(s, dtype == EIK_F64, (hipStream_t)stream));
+    return EIK_OK;
+}
+
+int eik_path2d_safe_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, const double init[2], const double end[2],
+                        double tau, double* out, int64_t cap, int64_t* n_out, int* status, int64_t info[4]) {
+    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
+    if (!init || !end || cap < 2 || H < 3 || W < 3 || !(tau > 0)) return set_err(c, EIK_ERR_ARG, "bad path arguments");
+    if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = H * W;
+    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
+    HIPCHK(c, c->work.ensure(sizeof(double) * 2 * cap + 128));
+    double* d_out = (double*)c->work.p;
+    int64_t* d_n = (int64_t*)(d_out + 2 * cap);  // n | info[4] | status
+    int64_t* d_info = d_n + 1;
+    int* d_st = (int*)(d_info + 4);
+    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));
+    int rc = eik_path2d_safe_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, d_info, c->stream);
+    if (rc) return rc;
+    int64_t h[5] = {0, 0, 0, 0, 0};
+    int st = 0;
+    HIPCHK(c, hipMemcpyAsync(h, d_n, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int64_t nn = h[0] > cap ? cap : h[0];
+    if (nn > 0) HIPCHK(c, hipMemcpy(out, d_out, sizeof(double) * 2 * nn, hipMemcpyDeviceToHost));
+    *n_out = nn;
+    *status = st;
+    if (info)
+        for (int k = 0; k < 4; ++k) info[k] = h[1 + k];
+    return EIK_OK;
+}
+
+int eik_path2d_safe_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
+                              const int32_t* map_of, const double* inits, const double* ends, double tau,
+                              double* d_out, int64_t cap, int64_t* d_n_out, int* d_status, int64_t* d_info,
+                              void* stream) {
+    if (c && tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
+    GdmSafeBatchArgs s{};
+    DescBlock* blk = nullptr;
+    int rc = batch_stage(c, 2, d_T, B, H, W, 1, P, map_of, inits, ends, tau, d_out, cap, d_n_out, d_status,
+                         (hipStream_t)stream, s.b, &blk);
+    if (rc) return rc;
+    s.stall = safe_stall(tau);
+    s.info = d_info;
+    HIPCHK(c, gdm2d_safe_batch(s, dtype == EIK_F64, (hipStream_t)stream));
+    HIPCHK(c, hipEventRecord(blk->ev, (hipStream_t)stream));
+    return EIK_OK;
+}
+
+int eik_path2d_safe_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int64_t W, int64_t P,
+                              const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
+                              int64_t cap, int64_t* n_out, int* status, int64_t* info) {
+    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched path: NULL argument") : EIK_ERR_ARG;
+    int rc = batch_check(c, 2, B, H, W, 1, P, map_of, inits, ends, tau, cap);
+    if (rc) return rc;
+    if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = B * H * W;
+    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
+    // device results in c->work: out [P][cap][2] | info [P][4] | n_out [P] | status [P]
+    HIPCHK(c, c->work.ensure(sizeof(double) * 2 * cap * P + (5 * sizeof(int64_t) + sizeof(int)) * P + 64));
+    double* d_out = (double*)c->work.p;
+    int64_t* d_info = (int64_t*)(d_out + 2 * cap * P);
+    int64_t* d_n = d_info + 4 * P;
+    int* d_st = (int*)(d_n + P);
+    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));  // the B fields, once
+    rc = eik_path2d_safe_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau, d_out, cap, d_n, d_st,
+                                   d_info, c->stream);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
+        return rc;
+    }
+    if (info) HIPCHK(c, hipMemcpyAsync(info, d_info, sizeof(int64_t) * 4 * P, hipMemcpyDeviceToHost, c->stream));
+    return batch_fetch(c, 2, P, cap, d_out, d_n, d_st, out, n_out, status);
+}
+
 int eik_plan2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,
                          const double* starts, double tau, double* paths, int64_t cap, int64_t* n_out, int* status,
                          float* T_out) {

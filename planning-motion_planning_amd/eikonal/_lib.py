@@ -12,6 +12,7 @@ EIK_OK, EIK_ERR_ARG, EIK_ERR_HIP, EIK_ERR_NOMEM, EIK_ERR_NOCONVERGE, EIK_ERR_UNR
     0, -1, -2, -3, -4, -5, -6
 EIK_F32, EIK_F64 = 0, 1
 PATH_DONE, PATH_FALLBACK, PATH_ERROR = 0, 1, 2
+PATH_STUCK = 3  # the safe walker only (path2d_safe*): no lower neighbour, or out of iterations
 OPT_MAX_ROUNDS, OPT_SYNC_EVERY, OPT_TIMING, OPT_GRID, OPT_TOL, OPT_DELTA = 0, 1, 2, 3, 4, 5
 OPT_MODE, OPT_QTIMEOUT, OPT_MAX_VISITS, OPT_PASSES, OPT_FRESH_FIRST, OPT_SCHED, OPT_PATH_LOOP = 6, 7, 8, 9, 10, 11, 12
 OPT_FRONTS_CAP, OPT_LIVE_PACK, OPT_PRIO, OPT_LAYER_PLANAR, OPT_PRIO_RING, OPT_PRIO_DISPATCH = 13, 14, 15, 16, 17, 18
@@ -204,6 +205,14 @@ def lib():
                                            i64, _i64p, _i32p]
         L.eik_plan2d_batch_f32.argtypes = [vp, _f32p, i64, i64, i64, _i64p, _f64p, C.c_double, _f64p, i64, _i64p,
                                            _i32p, vp]
+        # obstacle-safe 2D paths: the entries above plus the info words (nullable, int64[4] per path)
+        L.eik_path2d_safe_dev.argtypes = [vp, vp, C.c_int, i64, i64, _f64p, _f64p, C.c_double, vp, i64, vp, vp, vp, vp]
+        L.eik_path2d_safe_f64.argtypes = [vp, _f64p, i64, i64, _f64p, _f64p, C.c_double, _f64p, i64, P(i64), P(C.c_int),
+                                          vp]
+        L.eik_path2d_safe_batch_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, i64, vp, _f64p, _f64p, C.c_double, vp,
+                                                i64, vp, vp, vp, vp]
+        L.eik_path2d_safe_batch_f64.argtypes = [vp, _f64p, i64, i64, i64, i64, vp, _f64p, _f64p, C.c_double, _f64p,
+                                                i64, _i64p, _i32p, vp]
         # incremental re-solve: rects / kinds are nullable host arrays (passed as an address or None)
         L.eik_fim2d_update.argtypes = [vp, vp, vp, i64, vp]
         L.eik_fim2d_resolve.argtypes = [vp, vp, vp, i64, vp]
@@ -273,6 +282,7 @@ EXPORTED = [
     "eik_fim3dl_create", "eik_fim3dl_start", "eik_last_form",
     "eik_path2d_batch_dev", "eik_path2d_batch_f64", "eik_path3d_batch_dev", "eik_path3d_batch_f64",
     "eik_plan2d_batch_f32",
+    "eik_path2d_safe_dev", "eik_path2d_safe_f64", "eik_path2d_safe_batch_dev", "eik_path2d_safe_batch_f64",
     "eik_fim2d_update", "eik_fim2d_resolve", "eik_fim2d_adopt", "eik_fim2d_update_info",
     "eik_tmap2d_update_f32", "eik_tmap2d_update_f64",
     "eik_fim2d_start_seeds", "eik_fim2d_solve_seeds", "eik_labels2d_dev", "eik_tmap2d_seeds_f32",
@@ -535,7 +545,7 @@ class Context:
 
     # -- batched paths (no reference counterpart): P walks in one launch, each bit-identical to the
     # single call on its field
-    def _path_batch(self, dim, T, inits, ends, tau, map_of, cap):
+    def _path_batch(self, dim, T, inits, ends, tau, map_of, cap, safe=False):
         T = np.ascontiguousarray(T, dtype=np.float64)
         if T.ndim == dim:
             T = T[None]
@@ -553,10 +563,17 @@ class Context:
         m = None if map_of is None else np.ascontiguousarray(map_of, np.int32).reshape(-1)
         if m is not None and len(m) != P:
             raise ValueError(f"{len(m)} map_of entries for {P} paths")
+        if cap is None and safe and not 0 < tau <= 1:
+            cap = 2  # (the library answers a bad tau with EIK_ERR_ARG)
         cap = int(round(15000 / tau)) + 4 if cap is None else int(cap)
         out = np.empty((max(P, 1), max(cap, 1), dim))
         n, st = np.zeros(max(P, 1), np.int64), np.zeros(max(P, 1), np.int32)
         mp = None if m is None else m.ctypes.data
+        if safe:  # the obstacle-safe 2D walker, with its info words
+            info = np.zeros((max(P, 1), 4), np.int64)
+            self._chk(lib().eik_path2d_safe_batch_f64(self._h, T, T.shape[0], T.shape[1], T.shape[2], P, mp, inits,
+                                                      ends, float(tau), out, cap, n, st, info.ctypes.data))
+            return [(out[p, : n[p]].copy(), int(st[p]), info[p].copy()) for p in range(P)]
         if dim == 2:
             self._chk(lib().eik_path2d_batch_f64(self._h, T, T.shape[0], T.shape[1], T.shape[2], P, mp, inits, ends,
                                                  float(tau), out, cap, n, st))
@@ -570,6 +587,27 @@ class Context:
         one node or P of them, map_of the field of each path (None: path p on field p when P == B,
         all on field 0 when B == 1) -> [(path (K, 2), status)] as P path2d calls would return."""
         return self._path_batch(2, T, inits, ends, tau, map_of, cap)
+
+    # -- obstacle-safe 2D paths (eik_path2d_safe_*, no reference counterpart): blocked steps and stalls
+    # go to an integer descent instead of the reference's truncation; 0 < tau <= 1
+    def path2d_safe(self, T, init, end, tau=0.5):
+        """-> (path (K, 2), status, info int64[4]): PATH_DONE, PATH_STUCK or PATH_ERROR; info = fallbacks
+        taken, points dropped, the first iteration in integer mode (-1: never), iterations run."""
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        H, W = T.shape
+        cap = int(round(15000 / tau)) + 4 if 0 < tau <= 1 else 2  # (a bad tau is the library's EIK_ERR_ARG)
+        out = np.empty((cap, 2))
+        n, st = i64(0), C.c_int(0)
+        info = np.zeros(4, np.int64)
+        self._chk(lib().eik_path2d_safe_f64(self._h, T, H, W, np.asarray(init, np.float64)[:2].copy(),
+                                            np.asarray(end, np.float64)[:2].copy(), float(tau), out, cap, C.byref(n),
+                                            C.byref(st), info.ctypes.data))
+        return out[: n.value].copy(), st.value, info
+
+    def path2d_safe_batch(self, T, inits, ends, tau=0.5, map_of=None, cap=None):
+        """P path2d_safe walks in one launch, arguments as path2d_batch -> [(path, status, info)], each as
+        the single call's; a path that is stuck or errors does not fail the call."""
+        return self._path_batch(2, T, inits, ends, tau, map_of, cap, safe=True)
 
     def path3d_batch(self, T, inits, ends, tau=0.5, map_of=None, cap=None):
         """path2d_batch for volumes (H x W x L or B x H x W x L, nodes (x, y, z)): as P path3d calls."""
