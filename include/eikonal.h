@@ -47,7 +47,10 @@ typedef enum {
     EIK_PATH_DONE = 0,     /* stop radius (< 1.5 cells) or step budget hit; end appended (:231-234) */
     EIK_PATH_FALLBACK = 1, /* NaN gradient: the reference's fallback returns a truncated path
                               (numpy-2 behaviour of FastMarching.py:178-218)                       */
-    EIK_PATH_ERROR = 2,    /* the reference raises out of getPathGDM (NaN point / out of range)     */
+    EIK_PATH_ERROR = 2,    /* the reference raises out of getPathGDM: a NaN point, an index out of
+                              range (3D: also a coordinate <= -1, which numpy's uint32 cast turns
+                              into an index past every axis), int(round()) of a NaN or infinite
+                              coordinate in the NaN branch; the path as it stands is returned      */
     EIK_PATH_STUCK = 3     /* eik_path2d_safe_* only: no lower neighbour to descend to, or the
                               iteration budget ran out short of the stop radius; end NOT appended   */
 } eik_path_status;

@@ -20,7 +20,7 @@
  *   interpolatePoint  FastMarching.py:305-338    -> interp2()
  *   FM3D updateNode   FastMarching3D.py:19-101   -> update3d()
  *   FM3D computeTmap  FastMarching3D.py:126-145  -> orc_fmm3d()
- *   FM3D getPathGDM   FastMarching3D.py:198-271  -> orc_gdm3d()
+ *   FM3D getPathGDM   FastMarching3D.py:198-271  -> orc_gdm3d(), orc_gdm3d_events()
  *   FM3D interpolate  FastMarching3D.py:275-314  -> interp3()
  *
  * Narrow band: the reference keeps a list sorted with bisect_left and pops index 0, so among
@@ -567,16 +567,40 @@ static double npgrad(const double *T, int64_t H, int64_t W, int64_t L, int axis,
     return (c[st] - c[-st]) / 2.0;
 }
 
+/* np.uint32(np.fix(p)) of FM3D interpolatePoint :276-278, made total.  numpy on x86-64 casts
+ * through a 64-bit truncating conversion and keeps the low 32 bits: NaN and +-inf give 0, p <= -1
+ * gives 2^32 - |fix(p)|, far past any axis, so mapI[j,i,k] (:283) raises IndexError.  Restated
+ * without a cast of an out-of-range value: non-finite -> index 0; p <= -1 -> IndexError; p >= 2^31
+ * -> IndexError as well (numpy wraps those modulo 2^32; no axis is that long, and this restatement
+ * treats every such coordinate as outside the volume).  The cast itself only sees (-1, 2^31). */
+static int fix_index(double p, int64_t *idx) {
+    if (!isfinite(p)) { *idx = 0; return 0; }
+    if (p <= -1.0 || p >= 2147483648.0) { *idx = 0; return ORC_REF_INDEXERROR; }
+    *idx = (int64_t)p;
+    return 0;
+}
+
+/* int(round(p)) of :213-215 / :219-221 followed by np.uint32() and the index into totalCostMap:
+ * NaN raises ValueError and +-inf OverflowError (both returned as ORC_REF_VALUEERROR); a rounded
+ * value outside [0, 2^31) is an IndexError (as fix_index).  *r is set only on success. */
+static int rint_node(double p, int64_t *r) {
+    if (!isfinite(p)) return ORC_REF_VALUEERROR;
+    double t = nearbyint(p);
+    if (t <= -1.0 || t >= 2147483648.0) return ORC_REF_INDEXERROR;
+    *r = (int64_t)t;
+    return 0;
+}
+
 /* FM3D interpolatePoint :275-314 for the interior branch (the one the path can reach) */
 static double interp3_field(double px, double py, double pz, const double *T, int64_t H, int64_t W, int64_t L,
                             int axis, int *err) {
-    uint32_t i = (uint32_t)trunc(px), j = (uint32_t)trunc(py), k = (uint32_t)trunc(pz);
+    int64_t i, j, k;
     *err = 0;
-    if (i + 1 >= (uint32_t)W || j + 1 >= (uint32_t)H || k + 1 >= (uint32_t)L) {
+    if (fix_index(px, &i) || fix_index(py, &j) || fix_index(pz, &k) || i + 1 >= W || j + 1 >= H || k + 1 >= L) {
         *err = ORC_REF_INDEXERROR; /* a0..a7 are evaluated before the edge tests (:283-290) */
         return NAN;
     }
-    double a = px - i, b = py - j, c = pz - k;
+    double a = px - (double)i, b = py - (double)j, c = pz - (double)k;
 #define M(J, I, K) npgrad(T, H, W, L, axis, (J), (I), (K))
     double m000 = M(j, i, k), m010 = M(j, i + 1, k), m100 = M(j + 1, i, k), m001 = M(j, i, k + 1);
     double m110 = M(j + 1, i + 1, k), m011 = M(j, i + 1, k + 1), m101 = M(j + 1, i, k + 1), m111 = M(j + 1, i + 1, k + 1);
@@ -594,10 +618,13 @@ static double interp3_field(double px, double py, double pz, const double *T, in
 
 /* FM3D interpolatePoint on a plain map (helper fixture) */
 double orc_interp3(double px, double py, double pz, const double *M_, int64_t m, int64_t n, int64_t o, int *err) {
-    uint32_t i = (uint32_t)trunc(px), j = (uint32_t)trunc(py), k = (uint32_t)trunc(pz);
+    int64_t i, j, k;
     *err = 0;
-    if (i + 1 >= (uint32_t)n || j + 1 >= (uint32_t)m || k + 1 >= (uint32_t)o) { *err = ORC_REF_INDEXERROR; return NAN; }
-    double a = px - i, b = py - j, c = pz - k;
+    if (fix_index(px, &i) || fix_index(py, &j) || fix_index(pz, &k) || i + 1 >= n || j + 1 >= m || k + 1 >= o) {
+        *err = ORC_REF_INDEXERROR;
+        return NAN;
+    }
+    double a = px - (double)i, b = py - (double)j, c = pz - (double)k;
 #define M(J, I, K) M_[((J) * n + (I)) * o + (K)]
     double a0 = M(j, i, k);
     double a1 = M(j, i + 1, k) - M(j, i, k);
@@ -613,9 +640,16 @@ double orc_interp3(double px, double py, double pz, const double *M_, int64_t m,
 
 static inline double norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
 
-/* FM3D getPathGDM :198-271.  init/end are (x, y, z). out: (max_out x 3). */
-int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *init, const double *end, double tau,
-              double *out, int64_t max_out, int64_t *n_out, int *status) {
+/* FM3D getPathGDM :198-271.  init/end are (x, y, z). out: (max_out x 3).  ev (may be NULL) counts
+ * what the walk did, so that a test can tell which branches a crafted volume takes:
+ *   ev[0] entries of the NaN branch (:212)         ev[3] neighbour reads whose index wrapped (:233-249)
+ *   ev[1] most points popped in one entry          ev[4] normalised steps (:256-261)
+ *   ev[2] points popped by the isinf loop (:217)   ev[5] steps taken (points appended at :261/:264) */
+int orc_gdm3d_events(const double *T, int64_t H, int64_t W, int64_t L, const double *init, const double *end,
+                     double tau, double *out, int64_t max_out, int64_t *n_out, int *status, int64_t *ev) {
+    int64_t ev_local[6];
+    if (!ev) ev = ev_local;
+    memset(ev, 0, 6 * sizeof *ev);
     if (!T || !init || !end || !out || !n_out || !status || max_out < 2 || !(tau > 0)) return ORC_ERR_ARG;
     int64_t n = 0;
 #define PUSH3(X, Y, Z)                               \
@@ -626,8 +660,17 @@ int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *in
         out[3 * n + 2] = (Z);                        \
         ++n;                                         \
     } while (0)
+#define RAISE(CODE)            \
+    do {                       \
+        *status = GDM_ERROR;   \
+        *n_out = n;            \
+        return (CODE);         \
+    } while (0)
+    *n_out = 0;
+    *status = GDM_ERROR;
     PUSH3(init[0], init[1], init[2]);
-    long steps = (long)nearbyint(15000.0 / tau); /* int(round(15000/tau)) :207 */
+    double dsteps = nearbyint(15000.0 / tau); /* int(round(15000/tau)) :207 */
+    long steps = dsteps < 4e18 ? (long)dsteps : (long)4e18;
     *status = GDM_DONE;
     static const int off[6][3] = {{0, -1, 0}, {0, 1, 0}, {-1, 0, 0}, {1, 0, 0}, {0, 0, -1}, {0, 0, 1}};
     for (long k = 0; k < steps; ++k) {
@@ -636,35 +679,40 @@ int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *in
         double dx = interp3_field(g[0], g[1], g[2], T, H, W, L, 1, &e1); /* G1: axis 1 (x) */
         double dy = interp3_field(g[0], g[1], g[2], T, H, W, L, 0, &e2); /* G2: axis 0 (y) */
         double dz = interp3_field(g[0], g[1], g[2], T, H, W, L, 2, &e3); /* G3: axis 2 (z) */
-        if (e1 || e2 || e3) { *status = GDM_ERROR; *n_out = n; return ORC_REF_INDEXERROR; }
+        if (e1 || e2 || e3) RAISE(ORC_REF_INDEXERROR);
         if (isnan(dx) || isnan(dy) || isnan(dz)) { /* :212-253 */
-            int64_t nx = (int64_t)nearbyint(g[0]), ny = (int64_t)nearbyint(g[1]), nz = (int64_t)nearbyint(g[2]);
-            for (;;) { /* :217-222 */
-                if (nx < 0 || ny < 0 || nz < 0 || nx >= W || ny >= H || nz >= L) {
-                    *status = GDM_ERROR; *n_out = n; return ORC_REF_INDEXERROR;
-                }
+            int64_t nx = 0, ny = 0, nz = 0, pops = 0;
+            int rc;
+            ++ev[0];
+            for (;;) { /* :213-222 */
+                const double *q = out + 3 * (n - 1);
+                if ((rc = rint_node(q[0], &nx)) || (rc = rint_node(q[1], &ny)) || (rc = rint_node(q[2], &nz)))
+                    RAISE(rc);
+                if (nx >= W || ny >= H || nz >= L) RAISE(ORC_REF_INDEXERROR);
                 if (!isinf(T[(ny * W + nx) * L + nz])) break;
                 --n;
-                if (n == 0) { *status = GDM_ERROR; *n_out = 0; return ORC_REF_INDEXERROR; }
-                const double *q = out + 3 * (n - 1);
-                nx = (int64_t)nearbyint(q[0]);
-                ny = (int64_t)nearbyint(q[1]);
-                nz = (int64_t)nearbyint(q[2]);
+                ++pops;
+                ++ev[2];
+                if (pops > ev[1]) ev[1] = pops;
+                if (n == 0) RAISE(ORC_REF_INDEXERROR); /* gamma[-1] of an empty path */
             }
             if (n > 0) { /* :223-227 */
                 while (norm3(out[3 * (n - 1)] - nx, out[3 * (n - 1) + 1] - ny, out[3 * (n - 1) + 2] - nz) < 1) {
                     --n;
+                    ++pops;
                     if (n == 0) break;
                 }
             }
+            if (pops > ev[1]) ev[1] = pops;
             PUSH3((double)nx, (double)ny, (double)nz); /* :229 */
             double curT = T[(ny * W + nx) * L + nz];   /* :230 */
             for (int q = 0; q < 6; ++q) {              /* :231-253 */
                 int64_t cx = nx + off[q][0], cy = ny + off[q][1], cz = nz + off[q][2];
+                if (cx < 0 || cy < 0 || cz < 0) ++ev[3];
                 if (cx < 0) cx += W; /* negative indices wrap (python) */
                 if (cy < 0) cy += H;
                 if (cz < 0) cz += L;
-                if (cx >= W || cy >= H || cz >= L) { *status = GDM_ERROR; *n_out = n; return ORC_REF_INDEXERROR; }
+                if (cx >= W || cy >= H || cz >= L) RAISE(ORC_REF_INDEXERROR);
                 double tc = T[(cy * W + cx) * L + cz];
                 if (tc < curT) {
                     curT = tc;
@@ -678,6 +726,7 @@ int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *in
         double nrm = sqrt(pow(dx, 2) + pow(dy, 2) + pow(dz, 2)); /* :255 */
         double ax, ay, az;
         if (nrm < 0.01) { /* :256-261 */
+            ++ev[4];
             ax = g[0] - tau * (dx / nrm);
             ay = g[1] - tau * (dy / nrm);
             az = g[2] - tau * (dz / nrm);
@@ -686,6 +735,7 @@ int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *in
             ay = g[1] - tau * dy;
             az = g[2] - tau * dz;
         }
+        ++ev[5];
         if (isnan(ax) || isnan(ay) || isnan(az)) { *status = GDM_ERROR; PUSH3(ax, ay, az); *n_out = n; return ORC_OK; }
         PUSH3(ax, ay, az);
         if (norm3(ax - end[0], ay - end[1], az - end[2]) < 1.5) break; /* :266-267 */
@@ -694,6 +744,12 @@ int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *in
     *n_out = n;
     return ORC_OK;
 #undef PUSH3
+#undef RAISE
+}
+
+int orc_gdm3d(const double *T, int64_t H, int64_t W, int64_t L, const double *init, const double *end, double tau,
+              double *out, int64_t max_out, int64_t *n_out, int *status) {
+    return orc_gdm3d_events(T, H, W, L, init, end, tau, out, max_out, n_out, status, NULL);
 }
 
 /* ------------------------------------------------------------------ batch (baseline) */

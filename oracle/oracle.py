@@ -51,6 +51,7 @@ def lib():
         L.orc_fmm3d_trace.argtypes = [_dp, i64, i64, i64, _ip, C.c_void_p, _dp, _ip]
         L.orc_gdm3d.argtypes = [_dp, i64, i64, i64, _dp, _dp, C.c_double, _dp, i64, C.POINTER(i64),
                                 C.POINTER(C.c_int)]
+        L.orc_gdm3d_events.argtypes = L.orc_gdm3d.argtypes + [_ip]
         L.orc_set_strict.argtypes = [C.c_int]
         L.orc_fmm2d_batch.argtypes = [_dp, i64, i64, i64, _ip, _dp, C.c_int]
         _lib = L
@@ -196,15 +197,22 @@ def fm3d_early_from_full(cost, Tf, goal, start):
     return np.where(keep, Tf, np.inf)
 
 
-def gdm3d(T, init, end, tau=0.5, max_out=None):
-    """FastMarching3D.getPathGDM :198-271 -> (path (K,3), status)."""
+GDM3D_EVENTS = ("nan_entries", "deepest_backtrack", "inf_pops", "wrapped_reads", "normalised_steps", "steps")
+
+
+def gdm3d(T, init, end, tau=0.5, max_out=None, events=False):
+    """FastMarching3D.getPathGDM :198-271 -> (path (K,3), status), with events=True also the walk's
+    event counts as a dict keyed by GDM3D_EVENTS (orc_gdm3d_events)."""
     T = _f64(T)
     H, W, L = T.shape
     steps = int(round(15000 / tau))
     max_out = max_out or steps + 4
     out = np.empty((max_out, 3))
     n, st = i64(0), C.c_int(0)
-    lib().orc_gdm3d(T, H, W, L, _f64(init), _f64(end), float(tau), out, max_out, C.byref(n), C.byref(st))
+    ev = np.zeros(6, np.int64)
+    lib().orc_gdm3d_events(T, H, W, L, _f64(init), _f64(end), float(tau), out, max_out, C.byref(n), C.byref(st), ev)
+    if events:
+        return out[: n.value].copy(), st.value, dict(zip(GDM3D_EVENTS, ev.tolist()))
     return out[: n.value].copy(), st.value
 
 

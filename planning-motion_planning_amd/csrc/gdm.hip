@@ -666,10 +666,14 @@ __device__ __forceinline__ double sq3(double a, double b, double c) { return a *
 // LDS with only a compiler fence (and an LDS-count wait) -- a workgroup barrier would also wait
 // for the path's global stores.
 __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-// (uint32_t)trunc(x) and rint(x) as int: one conversion each (the hardware truncates and clamps
-// to the type's range, NaN -> 0).  The walker's coordinates are finite (a NaN point ends the walk)
-// and below 2^31: out-of-range values clamp to 0 / INT_MIN / INT_MAX, which fail the same range
-// tests as the 64-bit conversions did.
+// (uint32_t)trunc(x) and rint(x) as int: one conversion each.  The hardware truncates and CLAMPS to
+// the type's range (negative -> 0 for the unsigned form, NaN -> 0), which is not what the
+// reference's np.uint32(np.fix(p)) does: numpy on x86-64 gives index 0 for NaN and +-inf and
+// 2^32 - |fix(p)| for p <= -1, which raises IndexError at mapI[j,i,k] (FastMarching3D.py:283).  So
+// the general step uses a conversion's result as an index only for a coordinate in (-1, 2^31)
+// (where clamping is truncation: (-1, 0) -> 0, as numpy) and decides every other coordinate itself
+// (DESIGN 3.4b); a finite coordinate's clamped rint, INT_MIN / INT_MAX, fails the same range tests
+// as the exact value.  No index is formed from a clamped or wrapped conversion.
 __device__ __forceinline__ uint32_t cvt_u32(double x) {
     uint32_t r;
     asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(x));
@@ -938,8 +942,31 @@ __global__ __launch_bounds__(kP3Threads) void gdm3d_kernel(A arg) {
             if (fin) break;
         }
         EIK_P3PROBE(3);
-        const uint32_t i = cvt_u32(gx), j = cvt_u32(gy), kk = cvt_u32(gz);
-        if (i + 1 >= (uint64_t)W || j + 1 >= (uint64_t)H || kk + 1 >= (uint64_t)L) { status = kGdmError; break; }
+        // np.uint32(np.fix(p)) of :276-278 and the rint node of :213-215.  The hardware conversions
+        // clamp, so they are numpy's only for a coordinate in (-1, 2^31).  Every other coordinate
+        // shows in the integer results -- p <= -1, NaN and -inf convert to 0, p >= 2^31 and +inf to
+        // 2^31 or more, which fails the range test -- so the step pays three integer tests and
+        // decides those rare cases (and a point in a cell of a low face) in the block below: a
+        // finite coordinate <= -1 or past the last cell is the reference's IndexError, a non-finite
+        // one takes index 0 with its own fraction, as numpy's cast gives it, and has no rint node
+        // (-1: nothing is gathered for it; the NaN branch raises at its int(round())).
+        uint32_t i = cvt_u32(gx), j = cvt_u32(gy), kk = cvt_u32(gz);
+        int64_t rx = rint_i32(gx), ry = rint_i32(gy), rz = rint_i32(gz);
+        bool gfin = true;  // all three coordinates finite
+        if ((int64_t)i + 1 >= W || (int64_t)j + 1 >= H || (int64_t)kk + 1 >= L || i == 0u || j == 0u || kk == 0u) {
+            const bool fx = __builtin_isfinite(gx), fy = __builtin_isfinite(gy), fz = __builtin_isfinite(gz);
+            auto raises = [](double p, uint32_t u, int64_t len, bool fin) {
+                return fin ? p <= -1.0 || (int64_t)u + 1 >= len : len < 2;
+            };
+            if (raises(gx, i, W, fx) || raises(gy, j, H, fy) || raises(gz, kk, L, fz)) { status = kGdmError; break; }
+            if (!(fx && fy && fz)) {
+                gfin = false;
+                i = fx ? i : 0u;  // index 0 as such, not a clamped conversion's result
+                j = fy ? j : 0u;
+                kk = fz ? kk : 0u;
+                rx = ry = rz = -1;
+            }
+        }
         // fast path: while bj_lo <= j <= bj_hi (and for i, kk) the cube is in the current window and
         // not within kPre3 of an inner edge (or a build is pending): nothing to do this step
         if ((int)j < bj_lo || (int)j > bj_hi || (int)i < bi_lo || (int)i > bi_hi || (int)kk < bk_lo || (int)kk > bk_hi) {
@@ -977,7 +1004,6 @@ __global__ __launch_bounds__(kP3Threads) void gdm3d_kernel(A arg) {
             set_bounds();
         }
         EIK_P3PROBE(0);
-        const int64_t rx = rint_i32(gx), ry = rint_i32(gy), rz = rint_i32(gz);
         const bool rin = rx >= 0 && ry >= 0 && rz >= 0 && rx < W && ry < H && rz < L;
         // per-lane gather, kept in registers: lanes 0..23 the two T samples of one np.gradient value
         // (axis, corner), lanes 24..30 the node and its six neighbours (:244-252).  (The last two
@@ -1093,6 +1119,10 @@ __global__ __launch_bounds__(kP3Threads) void gdm3d_kernel(A arg) {
         dz = tri3(gsh[2], gx - i, gy - j, gz - kk);
         EIK_P3PROBE(1);
         if (__builtin_isnan(dx) || __builtin_isnan(dy) || __builtin_isnan(dz)) {  // :212-253
+            // int(round(NaN)) raises ValueError, int(round(+-inf)) OverflowError (:213-215), the
+            // path as it stands.  (The points popped below were current points of earlier steps:
+            // finite and in (-1, 2^31), so their 64-bit conversions are exact.)
+            if (!gfin) { status = kGdmError; break; }
             int64_t nx = rx, ny = ry, nz = rz;
             bool err = false;
             // fast: the node is in range and reached -- no back-tracking, the gathered values apply
