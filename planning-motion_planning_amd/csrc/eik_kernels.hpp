@@ -224,8 +224,9 @@ struct Gdm2dArgs {
     int64_t cap;
     int64_t* n_out;        // device
     int* status;           // device
-    int fused;             // EIK_OPT_PATH_LOOP: 2 single-exit loop + range-free sqrt/div, 1 single-exit loop,
-                           // 0 reference-structured loop (same path bits)
+    int fused;             // EIK_OPT_PATH_LOOP, the loop form: 0 reference-structured loop, 1 single-exit loop,
+                           // 2 = 1 + range-free sqrt/div, 3 = 2 with the divisions from the roots' reciprocals,
+                           // 4 = 3 on lane pairs (the default); any other value: 0.  Same path bits in all five.
 };
 hipError_t gdm2d(const Gdm2dArgs& a, bool f64, hipStream_t st);
 // fast-path arithmetic of the 2D walker vs the exact forms (gdm.hip): mismatch counts [3] + samples, device

@@ -2039,11 +2039,11 @@ int eik_selftest_walker_math(eik_ctx* c, int64_t n, uint64_t seed, int64_t misma
     return EIK_OK;
 }
 
-int eik_path2d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, const double init[2],
-                   const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
-                   void* stream) {
-    if (!c || !d_T || !init || !end || !d_out || !d_n_out || !d_status || cap < 2 || H < 3 || W < 3 || !(tau > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad path arguments") : EIK_ERR_ARG;
+static long path_steps(double tau) { return (long)std::nearbyint(15000.0 / tau); }  // round(15000/tau), FastMarching.py:173
+
+// the walk's arguments of the two single-path 2D device entries, from theirs
+static Gdm2dArgs path2d_args(const void* d_T, int64_t H, int64_t W, const double init[2], const double end[2], double tau,
+                             double* d_out, int64_t cap, int64_t* d_n_out, int* d_status, int fused) {
     Gdm2dArgs a;
     a.T = d_T;
     a.H = H;
@@ -2053,39 +2053,66 @@ int eik_path2d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W,
     a.ex = end[0];
     a.ey = end[1];
     a.tau = tau;
-    a.steps = (long)std::nearbyint(15000.0 / tau);  // round(15000/tau), FastMarching.py:173
+    a.steps = path_steps(tau);
     a.out = d_out;
     a.cap = cap;
     a.n_out = d_n_out;
     a.status = d_status;
-    a.fused = c->path_loop;
+    a.fused = fused;
+    return a;
+}
+
+int eik_path2d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, const double init[2],
+                   const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
+                   void* stream) {
+    if (!c || !d_T || !init || !end || !d_out || !d_n_out || !d_status || cap < 2 || H < 3 || W < 3 || !(tau > 0))
+        return c ? set_err(c, EIK_ERR_ARG, "bad path arguments") : EIK_ERR_ARG;
+    const Gdm2dArgs a = path2d_args(d_T, H, W, init, end, tau, d_out, cap, d_n_out, d_status, c->path_loop);
     HIPCHK(c, gdm2d(a, dtype == EIK_F64, (hipStream_t)stream));
     return EIK_OK;
 }
 
+extern "C++" {  // (a template among the C entries)
+// The synchronous single-path host entries (dim = 2 or 3) after their own argument checks: the field
+// (`cells` values) to c->T2; the device results in c->work, out [cap][dim] | n | info [4] (has_info)
+// | status; launch(d_out, d_n, d_st, d_info), an entry's *_dev call on c->stream; then n, status
+// and the info words, and the n rows.
+template <typename Launch>
+static int path_host(eik_ctx* c, int dim, const double* T, int64_t cells, double* out, int64_t cap, int64_t* n_out,
+                     int* status, bool has_info, int64_t* info, Launch&& launch) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->T2.ensure(sizeof(double) * cells));
+    HIPCHK(c, c->work.ensure(sizeof(double) * dim * cap + (has_info ? 128 : 64)));
+    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * cells, c->stream));
+    double* d_out = (double*)c->work.p;
+    int64_t* d_n = (int64_t*)(d_out + dim * cap);
+    int64_t* d_info = has_info ? d_n + 1 : nullptr;
+    int* d_st = (int*)(d_n + (has_info ? 5 : 1));
+    int rc = launch(d_out, d_n, d_st, d_info);
+    if (rc) return rc;
+    int64_t h[5] = {0, 0, 0, 0, 0};  // n | info
+    int st = 0;
+    HIPCHK(c, hipMemcpyAsync(h, d_n, sizeof(int64_t) * (has_info ? 5 : 1), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t nn = h[0] > cap ? cap : h[0];
+    // (as the entries always did: the safe one skips the copy of no rows, the others issue it)
+    if (nn > 0 || !has_info) HIPCHK(c, hipMemcpy(out, d_out, sizeof(double) * dim * nn, hipMemcpyDeviceToHost));
+    *n_out = nn;
+    *status = st;
+    if (info)
+        for (int k = 0; k < 4; ++k) info[k] = h[1 + k];
+    return EIK_OK;
+}
+}  // extern "C++"
+
 int eik_path2d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, const double init[2], const double end[2],
                    double tau, double* out, int64_t cap, int64_t* n_out, int* status) {
     if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    HIPCHK(c, c->work.ensure(sizeof(double) * 2 * cap + 64));
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));
-    double* d_out = (double*)c->work.p;
-    int64_t* d_n = (int64_t*)(d_out + 2 * cap);
-    int* d_st = (int*)(d_n + 1);
-    int rc = eik_path2d_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, c->stream);
-    if (rc) return rc;
-    int64_t nn = 0;
-    int st = 0;
-    HIPCHK(c, hipMemcpyAsync(&nn, d_n, sizeof nn, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nn > cap) nn = cap;
-    HIPCHK(c, hipMemcpy(out, d_out, sizeof(double) * 2 * nn, hipMemcpyDeviceToHost));
-    *n_out = nn;
-    *status = st;
-    return EIK_OK;
+    return path_host(c, 2, T, H * W, out, cap, n_out, status, false, nullptr,
+                     [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
+                         return eik_path2d_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, c->stream);
+                     });
 }
 
 // ---- batched paths: P walks in one launch (gdm.hip: gdm2d_kernel / gdm3d_kernel on GdmBatchArgs)
@@ -2169,7 +2196,7 @@ static int batch_stage(eik_ctx* c, int dim, const void* d_T, int64_t B, int64_t 
     a.P = P;
     a.desc = (*blk)->d;
     a.tau = tau;
-    a.steps = (long)std::nearbyint(15000.0 / tau);  // as the single entries
+    a.steps = path_steps(tau);
     a.out = d_out;
     a.cap = cap;
     a.n_out = d_n_out;
@@ -2195,14 +2222,43 @@ static int batch_fetch(eik_ctx* c, int dim, int64_t P, int64_t cap, const double
     return EIK_OK;
 }
 
-// the host entries' device results in c->work: out [P][cap][dim] | n_out [P] | status [P]
-static int batch_work(eik_ctx* c, int dim, int64_t P, int64_t cap, double** d_out, int64_t** d_n, int** d_st) {
-    HIPCHK(c, c->work.ensure(sizeof(double) * dim * cap * P + (sizeof(int64_t) + sizeof(int)) * P + 64));
+// the host entries' device results in c->work: out [P][cap][dim] | info [P][4] (d_info given) | n_out [P]
+// | status [P]
+static int batch_work(eik_ctx* c, int dim, int64_t P, int64_t cap, double** d_out, int64_t** d_n, int** d_st,
+                      int64_t** d_info = nullptr) {
+    HIPCHK(c, c->work.ensure(sizeof(double) * dim * cap * P + ((d_info ? 5 : 1) * sizeof(int64_t) + sizeof(int)) * P + 64));
     *d_out = (double*)c->work.p;
-    *d_n = (int64_t*)(*d_out + dim * cap * P);
+    int64_t* const words = (int64_t*)(*d_out + dim * cap * P);
+    if (d_info) *d_info = words;
+    *d_n = words + (d_info ? 4 * P : 0);
     *d_st = (int*)(*d_n + P);
     return EIK_OK;
 }
+
+extern "C++" {
+// The synchronous batched host entries (dim = 2 or 3) after their own argument checks: the B fields
+// (`cells` values in all) to c->T2, once; launch(d_out, d_n, d_st, d_info), an entry's *_batch_dev
+// call on c->stream; then the info words and batch_fetch.
+template <typename Launch>
+static int path_batch_host(eik_ctx* c, int dim, const double* T, int64_t cells, int64_t P, double* out, int64_t cap,
+                           int64_t* n_out, int* status, bool has_info, int64_t* info, Launch&& launch) {
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->T2.ensure(sizeof(double) * cells));
+    double* d_out;
+    int64_t *d_n, *d_info = nullptr;
+    int* d_st;
+    int rc = batch_work(c, dim, P, cap, &d_out, &d_n, &d_st, has_info ? &d_info : nullptr);
+    if (rc) return rc;
+    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * cells, c->stream));
+    rc = launch(d_out, d_n, d_st, d_info);
+    if (rc) {
+        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
+        return rc;
+    }
+    if (info) HIPCHK(c, hipMemcpyAsync(info, d_info, sizeof(int64_t) * 4 * P, hipMemcpyDeviceToHost, c->stream));
+    return batch_fetch(c, dim, P, cap, d_out, d_n, d_st, out, n_out, status);
+}
+}  // extern "C++"
 
 int eik_path2d_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
                          const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
@@ -2223,22 +2279,11 @@ int eik_path2d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int6
     if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched path: NULL argument") : EIK_ERR_ARG;
     int rc = batch_check(c, 2, B, H, W, 1, P, map_of, inits, ends, tau, cap);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = B * H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    double* d_out;
-    int64_t* d_n;
-    int* d_st;
-    rc = batch_work(c, 2, P, cap, &d_out, &d_n, &d_st);
-    if (rc) return rc;
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));  // the B fields, once
-    rc = eik_path2d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau, d_out, cap, d_n, d_st,
-                              c->stream);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
-        return rc;
-    }
-    return batch_fetch(c, 2, P, cap, d_out, d_n, d_st, out, n_out, status);
+    return path_batch_host(c, 2, T, B * H * W, P, out, cap, n_out, status, false, nullptr,
+                           [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
+                               return eik_path2d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau, d_out,
+                                                           cap, d_n, d_st, c->stream);
+                           });
 }
 
 // ---- the obstacle-safe 2D walker (gdm_safe.hip): the entries above with tau <= 1 and the info words
@@ -2251,21 +2296,7 @@ int eik_path2d_safe_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64
         return c ? set_err(c, EIK_ERR_ARG, "bad path arguments") : EIK_ERR_ARG;
     if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
     GdmSafeArgs s;
-    Gdm2dArgs& a = s.a;
-    a.T = d_T;
-    a.H = H;
-    a.W = W;
-    a.ix = init[0];
-    a.iy = init[1];
-    a.ex = end[0];
-    a.ey = end[1];
-    a.tau = tau;
-    a.steps = (long)std::nearbyint(15000.0 / tau);  // round(15000/tau), FastMarching.py:173
-    a.out = d_out;
-    a.cap = cap;
-    a.n_out = d_n_out;
-    a.status = d_status;
-    a.fused = 0;
+    s.a = path2d_args(d_T, H, W, init, end, tau, d_out, cap, d_n_out, d_status, 0);
     s.stall = safe_stall(tau);
     s.info = d_info;
     HIPCHK(c, gdm2d_safe(s, dtype == EIK_F64, (hipStream_t)stream));
@@ -2277,29 +2308,11 @@ int eik_path2d_safe_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, const
     if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
     if (!init || !end || cap < 2 || H < 3 || W < 3 || !(tau > 0)) return set_err(c, EIK_ERR_ARG, "bad path arguments");
     if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    HIPCHK(c, c->work.ensure(sizeof(double) * 2 * cap + 128));
-    double* d_out = (double*)c->work.p;
-    int64_t* d_n = (int64_t*)(d_out + 2 * cap);  // n | info[4] | status
-    int64_t* d_info = d_n + 1;
-    int* d_st = (int*)(d_info + 4);
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));
-    int rc = eik_path2d_safe_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, d_info, c->stream);
-    if (rc) return rc;
-    int64_t h[5] = {0, 0, 0, 0, 0};
-    int st = 0;
-    HIPCHK(c, hipMemcpyAsync(h, d_n, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int64_t nn = h[0] > cap ? cap : h[0];
-    if (nn > 0) HIPCHK(c, hipMemcpy(out, d_out, sizeof(double) * 2 * nn, hipMemcpyDeviceToHost));
-    *n_out = nn;
-    *status = st;
-    if (info)
-        for (int k = 0; k < 4; ++k) info[k] = h[1 + k];
-    return EIK_OK;
+    return path_host(c, 2, T, H * W, out, cap, n_out, status, true, info,
+                     [&](double* d_out, int64_t* d_n, int* d_st, int64_t* d_info) {
+                         return eik_path2d_safe_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, d_info,
+                                                    c->stream);
+                     });
 }
 
 int eik_path2d_safe_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
@@ -2326,24 +2339,11 @@ int eik_path2d_safe_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H,
     int rc = batch_check(c, 2, B, H, W, 1, P, map_of, inits, ends, tau, cap);
     if (rc) return rc;
     if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = B * H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    // device results in c->work: out [P][cap][2] | info [P][4] | n_out [P] | status [P]
-    HIPCHK(c, c->work.ensure(sizeof(double) * 2 * cap * P + (5 * sizeof(int64_t) + sizeof(int)) * P + 64));
-    double* d_out = (double*)c->work.p;
-    int64_t* d_info = (int64_t*)(d_out + 2 * cap * P);
-    int64_t* d_n = d_info + 4 * P;
-    int* d_st = (int*)(d_n + P);
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));  // the B fields, once
-    rc = eik_path2d_safe_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau, d_out, cap, d_n, d_st,
-                                   d_info, c->stream);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
-        return rc;
-    }
-    if (info) HIPCHK(c, hipMemcpyAsync(info, d_info, sizeof(int64_t) * 4 * P, hipMemcpyDeviceToHost, c->stream));
-    return batch_fetch(c, 2, P, cap, d_out, d_n, d_st, out, n_out, status);
+    return path_batch_host(c, 2, T, B * H * W, P, out, cap, n_out, status, true, info,
+                           [&](double* d_out, int64_t* d_n, int* d_st, int64_t* d_info) {
+                               return eik_path2d_safe_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau,
+                                                                d_out, cap, d_n, d_st, d_info, c->stream);
+                           });
 }
 
 int eik_plan2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,
@@ -2827,7 +2827,7 @@ int eik_path3d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W,
         a.end[i] = end[i];
     }
     a.tau = tau;
-    a.steps = (long)std::nearbyint(15000.0 / tau);  // int(round(15000/tau)), FastMarching3D.py:207
+    a.steps = path_steps(tau);  // int(round(15000/tau)), FastMarching3D.py:207
     a.out = d_out;
     a.cap = cap;
     a.n_out = d_n_out;
@@ -2839,26 +2839,10 @@ int eik_path3d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W,
 int eik_path3d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, int64_t L, const double init[3],
                    const double end[3], double tau, double* out, int64_t cap, int64_t* n_out, int* status) {
     if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W * L;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    HIPCHK(c, c->work.ensure(sizeof(double) * 3 * cap + 64));
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));
-    double* d_out = (double*)c->work.p;
-    int64_t* d_n = (int64_t*)(d_out + 3 * cap);
-    int* d_st = (int*)(d_n + 1);
-    int rc = eik_path3d_dev(c, c->T2.p, EIK_F64, H, W, L, init, end, tau, d_out, cap, d_n, d_st, c->stream);
-    if (rc) return rc;
-    int64_t nn = 0;
-    int st = 0;
-    HIPCHK(c, hipMemcpyAsync(&nn, d_n, sizeof nn, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (nn > cap) nn = cap;
-    HIPCHK(c, hipMemcpy(out, d_out, sizeof(double) * 3 * nn, hipMemcpyDeviceToHost));
-    *n_out = nn;
-    *status = st;
-    return EIK_OK;
+    return path_host(c, 3, T, H * W * L, out, cap, n_out, status, false, nullptr,
+                     [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
+                         return eik_path3d_dev(c, c->T2.p, EIK_F64, H, W, L, init, end, tau, d_out, cap, d_n, d_st, c->stream);
+                     });
 }
 
 int eik_path3d_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
@@ -2880,22 +2864,11 @@ int eik_path3d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int6
     if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched 3D path: NULL argument") : EIK_ERR_ARG;
     int rc = batch_check(c, 3, B, H, W, L, P, map_of, inits, ends, tau, cap);
     if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = B * H * W * L;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    double* d_out;
-    int64_t* d_n;
-    int* d_st;
-    rc = batch_work(c, 3, P, cap, &d_out, &d_n, &d_st);
-    if (rc) return rc;
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));  // the B volumes, once
-    rc = eik_path3d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, L, P, map_of, inits, ends, tau, d_out, cap, d_n, d_st,
-                              c->stream);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
-        return rc;
-    }
-    return batch_fetch(c, 3, P, cap, d_out, d_n, d_st, out, n_out, status);
+    return path_batch_host(c, 3, T, B * H * W * L, P, out, cap, n_out, status, false, nullptr,
+                           [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
+                               return eik_path3d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, L, P, map_of, inits, ends, tau,
+                                                           d_out, cap, d_n, d_st, c->stream);
+                           });
 }
 
 int eik_gradient2d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, double* gnx, double* gny) {

@@ -16,8 +16,9 @@
 
 #pragma clang fp contract(off)
 
-// the helpers, the step's range-free square root / division and the window machinery (LDS windows,
-// builder waves): shared with the obstacle-safe walker (gdm_safe.hip)
+// the helpers, the step's arithmetic (walk_step_*, its range-free square root / division), the window
+// machinery (LDS windows, the builder waves' loop, the walker's window state Walk2Win): the one copy
+// this walker and the obstacle-safe one (gdm_safe.hip) both run
 #include "gdm_walk.hpp"
 
 namespace eik {
@@ -64,76 +65,14 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
     }
     int64_t n = 1;
     const double tau = a.tau;
-    // window origins of the two buffers (scalars, not an indexed array: no private->LDS promotion)
-    int64_t wx0 = -((int64_t)1 << 40), wx1 = wx0, wy0 = wx0, wy1 = wx0;
-    int cur = 0, seq = 0;
-    bool pending = false;
-    const int64_t xmax = W > kPW ? W - kPW : 0, ymax = H > kPW ? H - kPW : 0;
-    auto issue = [&](int b, int64_t i, int64_t j) {  // build the window centred on (i, j) into b
-        int64_t x0 = i - kPW / 2, y0 = j - kPW / 2;
-        x0 = x0 > xmax ? xmax : x0 < 0 ? 0 : x0;
-        y0 = y0 > ymax ? ymax : y0 < 0 ? 0 : y0;
-        if (b) { wx1 = x0; wy1 = y0; } else { wx0 = x0; wy0 = y0; }
-        s.req_x0 = x0;
-        s.req_y0 = y0;
-        s.req_b = b;
-        __hip_atomic_store(&s.req_seq, ++seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-    auto wait_built = [&]() -> bool {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(&s.done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq * kBuilders) {
-            if (__builtin_amdgcn_s_memrealtime() - t0 > kPathSpin) return false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        return true;
-    };
-    auto inside = [&](int b, int64_t i, int64_t j) {
-        const int64_t x0 = b ? wx1 : wx0, y0 = b ? wy1 : wy0;
-        return i >= x0 && j >= y0 && i + 1 < x0 + kPW && j + 1 < y0 + kPW;
-    };
-    // Fast path: while lo_x <= i <= hi_x and lo_y <= j <= hi_y nothing has to happen this step
-    // (the corners lie in the current window and, unless a build is pending, not within
-    // kPrefetch of an inner edge) -- four int32 compares on the step's dependency chain instead
-    // of the window bookkeeping, which runs only when the bounds are crossed.
-    int lo_x = 1, hi_x = 0, lo_y = 1, hi_y = 0;  // empty: the first step takes the slow path
-    int cx0i = 0, cy0i = 0;                     // current window origin
-    auto set_bounds = [&]() {
-        const int64_t x0 = cur ? wx1 : wx0, y0 = cur ? wy1 : wy0;
-        cx0i = (int)x0;
-        cy0i = (int)y0;
-        lo_x = cx0i + (!pending && x0 > 0 ? kPrefetch : 0);
-        hi_x = cx0i + kPW - 2 - (!pending && x0 < xmax ? kPrefetch : 0);
-        lo_y = cy0i + (!pending && y0 > 0 ? kPrefetch : 0);
-        hi_y = cy0i + kPW - 2 - (!pending && y0 < ymax ? kPrefetch : 0);
-        hi_x = hi_x < (int)W - 2 ? hi_x : (int)W - 2;  // inside the bounds implies i + 1 < W, j + 1 < H
-        hi_y = hi_y < (int)H - 2 ? hi_y : (int)H - 2;
-    };
+    Walk2Win win(s, H, W);
     // Window bookkeeping of a step whose cell (i, j) left the fast bounds: errors (NaN point, out
-    // of range) set status and return false; else the corners are in window `cur` afterwards.
+    // of range, a build that never finished) set status and return false; else the corners are in
+    // window `win.cur` afterwards.
     auto slow_step = [&](uint32_t i, uint32_t j) -> bool {
         if (__builtin_isnan(px) || __builtin_isnan(py)) { status = kGdmError; return false; }
         if (i + 1 >= (uint64_t)W || j + 1 >= (uint64_t)H) { status = kGdmError; return false; }
-        if (!inside(cur, i, j)) {  // the 2 x 2 interpolation corners left the window
-            const int nb = seq == 0 ? 0 : 1 - cur;
-            bool have = false;
-            if (pending) {
-                pending = false;
-                if (!wait_built()) { status = kGdmError; return false; }
-                have = inside(nb, i, j);
-            }
-            if (!have) {
-                issue(nb, i, j);
-                if (!wait_built()) { status = kGdmError; return false; }
-            }
-            cur = nb;
-        }
-        const int64_t cx0 = cur ? wx1 : wx0, cy0 = cur ? wy1 : wy0;
-        if (!pending && ((i - cx0 < kPrefetch && cx0 > 0) || (cx0 + kPW - 2 - i < kPrefetch && cx0 < xmax) ||
-                         (j - cy0 < kPrefetch && cy0 > 0) || (cy0 + kPW - 2 - j < kPrefetch && cy0 < ymax))) {
-            issue(1 - cur, i, j);
-            pending = true;
-        }
-        set_bounds();
+        if (!win.cross(i, j)) { status = kGdmError; return false; }
         return true;
     };
     // NaN fallback (:178-218) as the reference behaves under numpy 2: the neighbour probe
@@ -162,66 +101,6 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
         }
         status = kGdmFallback;
     };
-    // One step's arithmetic from the four corners (g00, g01, g10, g11) of cell (i, j):
-    // :175-176 interpolation, :220-229 normalisation, :230 step.
-    struct StepOut {
-        double dx, dy, sx, sy;
-    };
-    auto step_math = [&](const double2& g00, const double2& g01, const double2& g10, const double2& g11, double fa,
-                         double fb) -> StepOut {
-        StepOut o;
-        o.dx = interp2_sel(fa, fb, g00.x, g01.x, g10.x, g11.x);  // :175
-        o.dy = interp2_sel(fa, fb, g00.y, g01.y, g10.y, g11.y);  // :176
-        // |(dx, dy)| is the same value in the test (:220) and both normalisations (:221-227)
-        const double nrm = __builtin_sqrt(o.dx * o.dx + o.dy * o.dy);
-        const double dxn = o.dx / nrm;  // both branches
-        // :220-224 (|g| < 0.01: unit step) or :225-229 (dy normalised with the normalised dx)
-        const double dyn = nrm < 0.01 ? o.dy / nrm : o.dy / __builtin_sqrt(dxn * dxn + o.dy * o.dy);
-        o.sx = px - tau * dxn;
-        o.sy = py - tau * dyn;
-        return o;
-    };
-    // step_math with interp2_general, sqrt_core and div_core (same bits where walk_odd is false,
-    // set in `odd`)
-    auto step_math_core = [&](const double2& g00, const double2& g01, const double2& g10, const double2& g11, double fa,
-                              double fb, bool& odd) -> StepOut {
-        StepOut o;
-        o.dx = interp2_general(fa, fb, g00.x, g01.x, g10.x, g11.x);
-        o.dy = interp2_general(fa, fb, g00.y, g01.y, g10.y, g11.y);
-        const double s1 = o.dx * o.dx + o.dy * o.dy;
-        const double nrm = sqrt_core(s1);
-        const double dxn = div_core(o.dx, nrm);
-        // both divisors computed, selected bitwise (a ?: here becomes a branch on the chain)
-        const double r2 = sqrt_core(dxn * dxn + o.dy * o.dy);
-        const long long small = -(long long)(nrm < 0.01);
-        const double den = __longlong_as_double((__double_as_longlong(nrm) & small) | (__double_as_longlong(r2) & ~small));
-        const double dyn = div_core(o.dy, den);
-        o.sx = px - tau * dxn;
-        o.sy = py - tau * dyn;
-        odd = walk_odd(o.dx, o.dy, s1);
-        return o;
-    };
-    // step_math_core with the divisions taken from the square roots' reciprocals (div_rs): the
-    // step's dependent f64 chain 45 -> 33 operations (LOOP 3)
-    auto step_math_rs = [&](const double2& g00, const double2& g01, const double2& g10, const double2& g11, double fa,
-                            double fb, bool& odd) -> StepOut {
-        StepOut o;
-        o.dx = interp2_general(fa, fb, g00.x, g01.x, g10.x, g11.x);
-        o.dy = interp2_general(fa, fb, g00.y, g01.y, g10.y, g11.y);
-        const double s1 = o.dx * o.dx + o.dy * o.dy;
-        double h1, h2;
-        const double nrm = sqrt_core_h(s1, h1);
-        const double dxn = div_rs(o.dx, nrm, h1);
-        const double r2 = sqrt_core_h(dxn * dxn + o.dy * o.dy, h2);
-        const long long small = -(long long)(nrm < 0.01);
-        const double den = __longlong_as_double((__double_as_longlong(nrm) & small) | (__double_as_longlong(r2) & ~small));
-        const double hd = __longlong_as_double((__double_as_longlong(h1) & small) | (__double_as_longlong(h2) & ~small));
-        const double dyn = div_rs(o.dy, den, hd);
-        o.sx = px - tau * dxn;
-        o.sy = py - tau * dyn;
-        odd = walk_odd(o.dx, o.dy, s1);
-        return o;
-    };
     // the point budget folded into the step count: point n = k + 1 is stored at step k (:173)
     const long kmax = a.steps < a.cap - 1 ? a.steps : a.cap - 1;
     long k = 0;
@@ -247,13 +126,13 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
         for (; k < kmax;) {
             uint32_t i, j;
             bool in, odd = false;
-            StepOut o;
+            WalkStep o;
             double fa, fb;
             if constexpr (LOOP == 4) {
                 double p = yl ? py : px, d = 0.0, pn = 0.0;
                 // this lane's fast bounds (x or y) as a half-open f64 range: lo <= p < hi + 1 (NaN
                 // fails it; p in (-1, 0) goes to the handler, which is exact anyway)
-                const double loc = yl ? lo_y : lo_x, hic = (yl ? hi_y : hi_x) + 1;
+                const double loc = yl ? win.lo_y : win.lo_x, hic = (yl ? win.hi_y : win.hi_x) + 1;
                 // Steps this loop may take without the stop test: none of them can come within 1.5
                 // of the goal (:231) -- a step moves each coordinate by at most |tau| (|dxn|, |dyn|
                 // <= 1), so k steps move at most k |tau| sqrt(2) (with slack for rounding) -- and
@@ -267,8 +146,8 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
                 // the corners' LDS address in vector registers: each lane scales its own cell
                 // index (x: 16 B per column, y: kPW x 16 B per row) and adds its partner's (DPP)
                 const unsigned sc = yl ? kPW * (unsigned)sizeof(double2) : (unsigned)sizeof(double2);
-                const unsigned c0 = (unsigned)(yl ? cy0i : cx0i) * sc;
-                const char* const base = reinterpret_cast<const char*>(s.g[cur]) + (yl ? sizeof(double) : 0);
+                const unsigned c0 = (unsigned)(yl ? win.cy0i : win.cx0i) * sc;
+                const char* const base = reinterpret_cast<const char*>(s.g[win.cur]) + (yl ? sizeof(double) : 0);
                 int kk = 0;
                 // One conditional branch per step: the point is stored and the state advanced before
                 // the exit test (the stores are in range -- n < cap -- and a step the handler below
@@ -335,19 +214,20 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
                 EIK_P2PROBE(0);
                 i = (uint32_t)__builtin_trunc(px);
                 j = (uint32_t)__builtin_trunc(py);
-                in = !__builtin_isnan(px + py) && (int)i >= lo_x && (int)i <= hi_x && (int)j >= lo_y && (int)j <= hi_y;
-                unsigned off = (unsigned)(((int)j - cy0i) * kPW + ((int)i - cx0i)) * (unsigned)sizeof(double2);
+                in = !__builtin_isnan(px + py) && (int)i >= win.lo_x && (int)i <= win.hi_x && (int)j >= win.lo_y &&
+                     (int)j <= win.hi_y;
+                unsigned off = (unsigned)(((int)j - win.cy0i) * kPW + ((int)i - win.cx0i)) * (unsigned)sizeof(double2);
                 off = off <= kWinBytes - (kPW + 2) * sizeof(double2) ? off : 0u;  // unsigned: negatives too
-                const double2* g = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(s.g[cur]) + off);
+                const double2* g = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(s.g[win.cur]) + off);
                 EIK_P2PROBE(1);
                 fa = px - i;
                 fb = py - j;
                 if constexpr (LOOP == 3)
-                    o = step_math_rs(g[0], g[1], g[kPW], g[kPW + 1], fa, fb, odd);
+                    o = walk_step_rs(g[0], g[1], g[kPW], g[kPW + 1], fa, fb, px, py, tau, odd);
                 else if constexpr (LOOP == 2)
-                    o = step_math_core(g[0], g[1], g[kPW], g[kPW + 1], fa, fb, odd);
+                    o = walk_step_core(g[0], g[1], g[kPW], g[kPW + 1], fa, fb, px, py, tau, odd);
                 else
-                    o = step_math(g[0], g[1], g[kPW], g[kPW + 1], fa, fb);
+                    o = walk_step_exact(g[0], g[1], g[kPW], g[kPW + 1], fa, fb, px, py, tau);
                 EIK_P2PROBE(2);
                 const double ex = o.sx - a.ex, ey = o.sy - a.ey;
                 const bool stop = ex * ex + ey * ey < 2.25;  // :231-232, as in the loop below
@@ -364,9 +244,9 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
             }
             if (!in || odd) {  // window bookkeeping (or an error), then this step again -- exactly
                 if (!in && !slow_step(i, j)) break;
-                const int li = (int)i - cx0i, lj = (int)j - cy0i;
-                o = step_math(s.g[cur][lj][li], s.g[cur][lj][li + 1], s.g[cur][lj + 1][li], s.g[cur][lj + 1][li + 1],
-                              fa, fb);
+                const int li = (int)i - win.cx0i, lj = (int)j - win.cy0i;
+                const auto& g = s.g[win.cur];
+                o = walk_step_exact(g[lj][li], g[lj][li + 1], g[lj + 1][li], g[lj + 1][li + 1], fa, fb, px, py, tau);
             }
             // the reference-structured loop's end of step
             const double ex = o.sx - a.ex, ey = o.sy - a.ey;
@@ -387,14 +267,15 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
             EIK_P2PROBE(0);
             const uint32_t i = (uint32_t)__builtin_trunc(px), j = (uint32_t)__builtin_trunc(py);
             // one test on the chain: NaN point, out of range, or window bookkeeping due
-            if (__builtin_isnan(px + py) || (int)i < lo_x || (int)i > hi_x || (int)j < lo_y || (int)j > hi_y) {
+            if (__builtin_isnan(px + py) || (int)i < win.lo_x || (int)i > win.hi_x || (int)j < win.lo_y ||
+                (int)j > win.hi_y) {
                 if (!slow_step(i, j)) break;
             }
             EIK_P2PROBE(1);
-            const int li = (int)i - cx0i, lj = (int)j - cy0i;
+            const int li = (int)i - win.cx0i, lj = (int)j - win.cy0i;
             const double fa = px - i, fb = py - j;
-            const StepOut o = step_math(s.g[cur][lj][li], s.g[cur][lj][li + 1], s.g[cur][lj + 1][li],
-                                        s.g[cur][lj + 1][li + 1], fa, fb);
+            const auto& g = s.g[win.cur];
+            const WalkStep o = walk_step_exact(g[lj][li], g[lj][li + 1], g[lj + 1][li], g[lj + 1][li + 1], fa, fb, px, py, tau);
             EIK_P2PROBE(2);
             // :231-232  sqrt(e) < 1.5  <=>  e < 2.25 for a correctly rounded sqrt (2.25 = 1.5^2 exactly)
             const double ex = o.sx - a.ex, ey = o.sy - a.ey;
@@ -490,40 +371,32 @@ hipError_t walker_math_selftest(long long n, unsigned long long seed, unsigned l
     return hipGetLastError();
 }
 
-hipError_t gdm2d(const Gdm2dArgs& a, bool f64, hipStream_t st) {
-    const dim3 g(1), b(kPathThreads);
-    if (f64) {
-        if (a.fused == 4)      hipLaunchKernelGGL((gdm2d_kernel<double, 4>), g, b, 0, st, a);
-        else if (a.fused == 3) hipLaunchKernelGGL((gdm2d_kernel<double, 3>), g, b, 0, st, a);
-        else if (a.fused == 2) hipLaunchKernelGGL((gdm2d_kernel<double, 2>), g, b, 0, st, a);
-        else if (a.fused == 1) hipLaunchKernelGGL((gdm2d_kernel<double, 1>), g, b, 0, st, a);
-        else                   hipLaunchKernelGGL((gdm2d_kernel<double, 0>), g, b, 0, st, a);
-    } else {
-        if (a.fused == 4)      hipLaunchKernelGGL((gdm2d_kernel<float, 4>), g, b, 0, st, a);
-        else if (a.fused == 3) hipLaunchKernelGGL((gdm2d_kernel<float, 3>), g, b, 0, st, a);
-        else if (a.fused == 2) hipLaunchKernelGGL((gdm2d_kernel<float, 2>), g, b, 0, st, a);
-        else if (a.fused == 1) hipLaunchKernelGGL((gdm2d_kernel<float, 1>), g, b, 0, st, a);
-        else                   hipLaunchKernelGGL((gdm2d_kernel<float, 0>), g, b, 0, st, a);
+// The runtime (f64, fused) as gdm2d_kernel<R, LOOP, A>, A = Gdm2dArgs or GdmBatchArgs; a `fused`
+// outside 1..4 is form 0.
+template <typename R, typename A>
+static void gdm2d_launch_form(const A& a, dim3 g, hipStream_t st) {
+    const dim3 b(kPathThreads);
+    switch (a.fused) {
+    case 4: hipLaunchKernelGGL((gdm2d_kernel<R, 4, A>), g, b, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((gdm2d_kernel<R, 3, A>), g, b, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((gdm2d_kernel<R, 2, A>), g, b, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((gdm2d_kernel<R, 1, A>), g, b, 0, st, a); break;
+    default: hipLaunchKernelGGL((gdm2d_kernel<R, 0, A>), g, b, 0, st, a); break;
     }
+}
+template <typename A>
+static hipError_t gdm2d_launch(const A& a, unsigned blocks, bool f64, hipStream_t st) {
+    if (f64)
+        gdm2d_launch_form<double>(a, dim3(blocks), st);
+    else
+        gdm2d_launch_form<float>(a, dim3(blocks), st);
     return hipGetLastError();
 }
 
+hipError_t gdm2d(const Gdm2dArgs& a, bool f64, hipStream_t st) { return gdm2d_launch(a, 1u, f64, st); }
+
 hipError_t gdm2d_batch(const GdmBatchArgs& a, bool f64, hipStream_t st) {
-    const dim3 g((unsigned)a.P), b(kPathThreads);
-    if (f64) {
-        if (a.fused == 4)      hipLaunchKernelGGL((gdm2d_kernel<double, 4, GdmBatchArgs>), g, b, 0, st, a);
-        else if (a.fused == 3) hipLaunchKernelGGL((gdm2d_kernel<double, 3, GdmBatchArgs>), g, b, 0, st, a);
-        else if (a.fused == 2) hipLaunchKernelGGL((gdm2d_kernel<double, 2, GdmBatchArgs>), g, b, 0, st, a);
-        else if (a.fused == 1) hipLaunchKernelGGL((gdm2d_kernel<double, 1, GdmBatchArgs>), g, b, 0, st, a);
-        else                   hipLaunchKernelGGL((gdm2d_kernel<double, 0, GdmBatchArgs>), g, b, 0, st, a);
-    } else {
-        if (a.fused == 4)      hipLaunchKernelGGL((gdm2d_kernel<float, 4, GdmBatchArgs>), g, b, 0, st, a);
-        else if (a.fused == 3) hipLaunchKernelGGL((gdm2d_kernel<float, 3, GdmBatchArgs>), g, b, 0, st, a);
-        else if (a.fused == 2) hipLaunchKernelGGL((gdm2d_kernel<float, 2, GdmBatchArgs>), g, b, 0, st, a);
-        else if (a.fused == 1) hipLaunchKernelGGL((gdm2d_kernel<float, 1, GdmBatchArgs>), g, b, 0, st, a);
-        else                   hipLaunchKernelGGL((gdm2d_kernel<float, 0, GdmBatchArgs>), g, b, 0, st, a);
-    }
-    return hipGetLastError();
+    return gdm2d_launch(a, (unsigned)a.P, f64, st);
 }
 
 // ---------------------------------------------------------------- 3D path (FM3D)
@@ -601,23 +474,7 @@ __device__ void build3(Path3Lds& s, const R* __restrict__ T, int64_t H, int64_t 
 
 template <typename R>
 __device__ __forceinline__ void path3_builder(Path3Lds& s, const R* __restrict__ T, int64_t H, int64_t W, int64_t L) {
-    const int w = (int)(threadIdx.x >> 6) - 1;
-    int seen = 0;
-    unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        const int q = __hip_atomic_load(&s.req_seq, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        if (q < 0) return;
-        if (q == seen) {
-            if (__builtin_amdgcn_s_memrealtime() - t0 > kPathSpin) return;  // walker gone: give up
-            __builtin_amdgcn_s_sleep(1);
-            continue;
-        }
-        seen = q;
-        build3<R>(s, T, H, W, L, s.req_b, s.req_y0, s.req_x0, s.req_z0, w);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(&s.done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        t0 = __builtin_amdgcn_s_memrealtime();
-    }
+    builder_loop(s, [&](int w) { build3<R>(s, T, H, W, L, s.req_b, s.req_y0, s.req_x0, s.req_z0, w); });
 }
 
 template <typename R>

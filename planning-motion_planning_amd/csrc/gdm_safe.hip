@@ -1,10 +1,11 @@
 // gdm_safe.hip -- the obstacle-safe 2D walker (eik_path2d_safe_*) on gfx950: its own
-// kernel next to gdm.hip's reference-faithful walker, which it leaves alone.
+// kernel next to gdm.hip's reference-faithful walker.  The two run one copy (gdm_walk.hpp) of the
+// step's arithmetic (walk_step_*), the window state (Walk2Win) and the builders.
 //
 // The rule (no reference counterpart beyond the cited lines; tests/path_safe_np.py restates it on the
 // host).  G' is computeGradient's (Gnx, Gny) with NaN at every node whose T is +inf.  Per iteration,
 // with p the last point:
-//   * gradient step (FastMarching.py:175-176, :220-230 -- the default walker's arithmetic and bits)
+//   * gradient step (FastMarching.py:175-176, :220-230 -- the default walker's walk_step_*: its bits)
 //     unless the interpolation of G' at p is NaN (a corner it uses is impassable, or the reference's
 //     own 0/0) or the walk is in integer mode;
 //   * else the fallback of :178-218 as intended (FastMarching3D.py:212-264 runs it): n = rint(p); while
@@ -31,48 +32,6 @@
 #include "gdm_walk.hpp"
 
 namespace eik {
-
-struct SafeStep {
-    double dx, dy, sx, sy;
-};
-// One step from the four corners of the point's cell, the default walker's exact form (gdm.hip
-// step_math): :175-176 interpolation with the a == 0 / b == 0 cases, :220-229 normalisation, :230.
-__device__ __forceinline__ SafeStep safe_step_exact(const double2& g00, const double2& g01, const double2& g10,
-                                                    const double2& g11, double fa, double fb, double px, double py,
-                                                    double tau) {
-    SafeStep o;
-    o.dx = interp2_sel(fa, fb, g00.x, g01.x, g10.x, g11.x);
-    o.dy = interp2_sel(fa, fb, g00.y, g01.y, g10.y, g11.y);
-    const double nrm = __builtin_sqrt(o.dx * o.dx + o.dy * o.dy);
-    const double dxn = o.dx / nrm;
-    const double dyn = nrm < 0.01 ? o.dy / nrm : o.dy / __builtin_sqrt(dxn * dxn + o.dy * o.dy);
-    o.sx = px - tau * dxn;
-    o.sy = py - tau * dyn;
-    return o;
-}
-// The same with the range-free square roots and the divisions taken from their reciprocals (gdm.hip
-// step_math_rs, the default walker's loop form 3): the same bits wherever `odd` comes back false,
-// which eik_selftest_walker_math vouches for (counts[2], counts[4]).
-__device__ __forceinline__ SafeStep safe_step_rs(const double2& g00, const double2& g01, const double2& g10,
-                                                 const double2& g11, double fa, double fb, double px, double py,
-                                                 double tau, bool& odd) {
-    SafeStep o;
-    o.dx = interp2_general(fa, fb, g00.x, g01.x, g10.x, g11.x);
-    o.dy = interp2_general(fa, fb, g00.y, g01.y, g10.y, g11.y);
-    const double s1 = o.dx * o.dx + o.dy * o.dy;
-    double h1, h2;
-    const double nrm = sqrt_core_h(s1, h1);
-    const double dxn = div_rs(o.dx, nrm, h1);
-    const double r2 = sqrt_core_h(dxn * dxn + o.dy * o.dy, h2);
-    const long long small = -(long long)(nrm < 0.01);
-    const double den = __longlong_as_double((__double_as_longlong(nrm) & small) | (__double_as_longlong(r2) & ~small));
-    const double hd = __longlong_as_double((__double_as_longlong(h1) & small) | (__double_as_longlong(h2) & ~small));
-    const double dyn = div_rs(o.dy, den, hd);
-    o.sx = px - tau * dxn;
-    o.sy = py - tau * dyn;
-    odd = walk_odd(o.dx, o.dy, s1);
-    return o;
-}
 
 __device__ __forceinline__ const Gdm2dArgs& safe_walk(const GdmSafeArgs& s) { return s.a; }
 __device__ __forceinline__ const GdmBatchArgs& safe_walk(const GdmSafeBatchArgs& s) { return s.b; }
@@ -110,71 +69,13 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_safe_kernel(A arg) {
     out[1] = py;
     int64_t n = 1;
     const double tau = a.tau;
-    // ---- window bookkeeping: gdm2d_kernel's, restated (that kernel's code stays where it is)
-    int64_t wx0 = -((int64_t)1 << 40), wx1 = wx0, wy0 = wx0, wy1 = wx0;
-    int cur = 0, seq = 0;
-    bool pending = false;
-    const int64_t xmax = W > kPW ? W - kPW : 0, ymax = H > kPW ? H - kPW : 0;
-    auto issue = [&](int b, int64_t i, int64_t j) {  // build the window centred on (i, j) into b
-        int64_t x0 = i - kPW / 2, y0 = j - kPW / 2;
-        x0 = x0 > xmax ? xmax : x0 < 0 ? 0 : x0;
-        y0 = y0 > ymax ? ymax : y0 < 0 ? 0 : y0;
-        if (b) { wx1 = x0; wy1 = y0; } else { wx0 = x0; wy0 = y0; }
-        s.req_x0 = x0;
-        s.req_y0 = y0;
-        s.req_b = b;
-        __hip_atomic_store(&s.req_seq, ++seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    };
-    auto wait_built = [&]() -> bool {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        while (__hip_atomic_load(&s.done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq * kBuilders) {
-            if (__builtin_amdgcn_s_memrealtime() - t0 > kPathSpin) return false;
-            __builtin_amdgcn_s_sleep(1);
-        }
-        return true;
-    };
-    auto inside = [&](int b, int64_t i, int64_t j) {
-        const int64_t x0 = b ? wx1 : wx0, y0 = b ? wy1 : wy0;
-        return i >= x0 && j >= y0 && i + 1 < x0 + kPW && j + 1 < y0 + kPW;
-    };
-    int lo_x = 1, hi_x = 0, lo_y = 1, hi_y = 0;  // fast bounds, empty: the first step takes the slow path
-    int cx0i = 0, cy0i = 0;                     // current window origin
-    auto set_bounds = [&]() {
-        const int64_t x0 = cur ? wx1 : wx0, y0 = cur ? wy1 : wy0;
-        cx0i = (int)x0;
-        cy0i = (int)y0;
-        lo_x = cx0i + (!pending && x0 > 0 ? kPrefetch : 0);
-        hi_x = cx0i + kPW - 2 - (!pending && x0 < xmax ? kPrefetch : 0);
-        lo_y = cy0i + (!pending && y0 > 0 ? kPrefetch : 0);
-        hi_y = cy0i + kPW - 2 - (!pending && y0 < ymax ? kPrefetch : 0);
-        hi_x = hi_x < (int)W - 2 ? hi_x : (int)W - 2;
-        hi_y = hi_y < (int)H - 2 ? hi_y : (int)H - 2;
-    };
+    Walk2Win win(s, H, W);
     // the cell (i, j) of a valid point left the fast bounds: switch / prefetch windows; false: a build
     // never finished (status set)
     auto slow_step = [&](int64_t i, int64_t j) -> bool {
-        if (!inside(cur, i, j)) {
-            const int nb = seq == 0 ? 0 : 1 - cur;
-            bool have = false;
-            if (pending) {
-                pending = false;
-                if (!wait_built()) { status = kGdmError; return false; }
-                have = inside(nb, i, j);
-            }
-            if (!have) {
-                issue(nb, i, j);
-                if (!wait_built()) { status = kGdmError; return false; }
-            }
-            cur = nb;
-        }
-        const int64_t cx0 = cur ? wx1 : wx0, cy0 = cur ? wy1 : wy0;
-        if (!pending && ((i - cx0 < kPrefetch && cx0 > 0) || (cx0 + kPW - 2 - i < kPrefetch && cx0 < xmax) ||
-                         (j - cy0 < kPrefetch && cy0 > 0) || (cy0 + kPW - 2 - j < kPrefetch && cy0 < ymax))) {
-            issue(1 - cur, i, j);
-            pending = true;
-        }
-        set_bounds();
-        return true;
+        if (win.cross(i, j)) return true;
+        status = kGdmError;
+        return false;
     };
     // ---- the rule
     // a NaN point, or one whose interpolation cell leaves the raster (trunc(x) + 1 >= W <=> x >= W - 1)
@@ -250,15 +151,26 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_safe_kernel(A arg) {
         // below then takes that iteration with the same decisions.  The LDS address of a cell outside
         // the bounds is clamped into the window (its values are discarded), the stall rule's node into
         // the raster (a point off the raster leaves before its T is used).
+        // Code placement, this one instantiation only.  The run loop below and the integer-mode loop
+        // are sensitive to where they start: in <double, GdmSafeArgs> the compiler's code ahead of them
+        // is one dword shorter than it was before the walkers shared Walk2Win, and with byte-identical
+        // loops four bytes earlier the fp64 single walk measured 1.4-1.9 % (gradient phase) and 4 %
+        // (integer mode) slower -- twice as many of the loops' 8-byte instructions then cross a 32 B /
+        // 64 B fetch line.  One dword here and ten ahead of the integer-mode loop (below), all
+        // outside the loops, put both loops back at the addresses they had; the run loops of the other
+        // three instantiations kept their start (mod 32) and get nothing.  This is tied to this
+        // compiler's output: when the code ahead of the loops changes again, measure
+        // (tools/path_safe_ab.py) and drop or move the pads.
+        if constexpr (std::is_same_v<R, double> && std::is_same_v<A, GdmSafeArgs>) asm volatile("s_nop 0");
         while (have_tq) {
             const uint32_t i = (uint32_t)__builtin_trunc(px), j = (uint32_t)__builtin_trunc(py);
-            const bool in = (int)(px >= 0.0) & (int)(py >= 0.0) & (int)((int)i >= lo_x) & (int)((int)i <= hi_x) &
-                            (int)((int)j >= lo_y) & (int)((int)j <= hi_y);
-            unsigned off = (unsigned)(((int)j - cy0i) * kPW + ((int)i - cx0i)) * (unsigned)sizeof(double2);
+            const bool in = (int)(px >= 0.0) & (int)(py >= 0.0) & (int)((int)i >= win.lo_x) & (int)((int)i <= win.hi_x) &
+                            (int)((int)j >= win.lo_y) & (int)((int)j <= win.hi_y);
+            unsigned off = (unsigned)(((int)j - win.cy0i) * kPW + ((int)i - win.cx0i)) * (unsigned)sizeof(double2);
             off = off <= kWinBytes - (kPW + 2) * sizeof(double2) ? off : 0u;  // unsigned: negatives too
-            const double2* g = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(s.g[cur]) + off);
+            const double2* g = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(s.g[win.cur]) + off);
             bool odd;
-            const SafeStep o = safe_step_rs(g[0], g[1], g[kPW], g[kPW + 1], px - (double)i, py - (double)j, px, py, tau, odd);
+            const WalkStep o = walk_step_rs(g[0], g[1], g[kPW], g[kPW + 1], px - (double)i, py - (double)j, px, py, tau, odd);
             const bool lower = tq < tlow;
             const double ntlow = lower ? tq : tlow;
             const long nstale = lower ? 0 : stale + 1;
@@ -280,16 +192,16 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_safe_kernel(A arg) {
         }
         if (bad(px, py)) { ++k; status = kGdmError; break; }
         const int64_t i = (int64_t)px, j = (int64_t)py;
-        if (i < lo_x || i > hi_x || j < lo_y || j > hi_y) {
+        if (i < win.lo_x || i > win.hi_x || j < win.lo_y || j > win.hi_y) {
             if (!slow_step(i, j)) { ++k; break; }
         }
-        const int li = (int)i - cx0i, lj = (int)j - cy0i;
+        const int li = (int)i - win.cx0i, lj = (int)j - win.cy0i;
         const double fa = px - (double)i, fb = py - (double)j;
-        const double2 g00 = s.g[cur][lj][li], g01 = s.g[cur][lj][li + 1], g10 = s.g[cur][lj + 1][li],
-                      g11 = s.g[cur][lj + 1][li + 1];
+        const auto& gw = s.g[win.cur];
+        const double2 g00 = gw[lj][li], g01 = gw[lj][li + 1], g10 = gw[lj + 1][li], g11 = gw[lj + 1][li + 1];
         bool odd;
-        SafeStep o = safe_step_rs(g00, g01, g10, g11, fa, fb, px, py, tau, odd);
-        if (odd) o = safe_step_exact(g00, g01, g10, g11, fa, fb, px, py, tau);
+        WalkStep o = walk_step_rs(g00, g01, g10, g11, fa, fb, px, py, tau, odd);
+        if (odd) o = walk_step_exact(g00, g01, g10, g11, fa, fb, px, py, tau);
         stale_test();  // its load had the step's arithmetic to arrive
         ++k;
         if (integer || __builtin_isnan(o.dx) || __builtin_isnan(o.dy)) {
@@ -317,6 +229,9 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_safe_kernel(A arg) {
     if (integer && status == kGdmDone && !reached) {
         int64_t cx = (int64_t)px, cy = (int64_t)py;
         double tc = tq;
+        // (code placement, as ahead of the gradient phase's run loop: ten dwords, once per walk)
+        if constexpr (std::is_same_v<R, double> && std::is_same_v<A, GdmSafeArgs>)
+            asm volatile(".rept 10\n s_nop 0\n .endr");
         while (k < kmax) {
             ++k;
             if (cx + 1 >= W || cy + 1 >= H || n >= a.cap) { status = kGdmError; break; }

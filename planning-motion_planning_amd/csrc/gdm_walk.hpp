@@ -1,7 +1,8 @@
 // gdm_walk.hpp -- what the 2D path kernels share (gdm.hip: the reference-faithful walker, all loop
 // forms; gdm_safe.hip: the obstacle-safe walker): the gradient and interpolation helpers, the
-// range-free f64 square root / division of the fast step, and the window machinery (LDS windows of
-// the normalised gradient, builder waves, prefetch distance).  Include it after
+// range-free f64 square root / division of the fast step, the step's arithmetic in its three forms
+// (walk_step_*), and the window machinery (LDS windows of the normalised gradient, builder waves and
+// their polling loop -- the 3D walker's too --, the walker's window state Walk2Win).  Include it after
 // `#pragma clang fp contract(off)`: every function here is IEEE fp64 without contraction.
 #pragma once
 #include "eik_common.hpp"
@@ -164,6 +165,74 @@ __device__ __forceinline__ bool walk_odd(double dx, double dy, double s1) {
            ((dy != 0.0) & (__builtin_fabs(dy) < tiny));
 }
 
+// One step's arithmetic from the four corners (g00, g01, g10, g11) of the point's cell and the
+// fractions (fa, fb) of (px, py) in it: :175-176 interpolation, :220-229 normalisation, :230 step.
+// The one copy both 2D walkers take their steps from.
+struct WalkStep {
+    double dx, dy, sx, sy;
+};
+// the exact form: interpolation with the a == 0 / b == 0 cases, the compiler's sqrt and division
+__device__ __forceinline__ WalkStep walk_step_exact(const double2& g00, const double2& g01, const double2& g10,
+                                                    const double2& g11, double fa, double fb, double px, double py,
+                                                    double tau) {
+    WalkStep o;
+    o.dx = interp2_sel(fa, fb, g00.x, g01.x, g10.x, g11.x);  // :175
+    o.dy = interp2_sel(fa, fb, g00.y, g01.y, g10.y, g11.y);  // :176
+    // |(dx, dy)| is the same value in the test (:220) and both normalisations (:221-227)
+    const double nrm = __builtin_sqrt(o.dx * o.dx + o.dy * o.dy);
+    const double dxn = o.dx / nrm;  // both branches
+    // :220-224 (|g| < 0.01: unit step) or :225-229 (dy normalised with the normalised dx)
+    const double dyn = nrm < 0.01 ? o.dy / nrm : o.dy / __builtin_sqrt(dxn * dxn + o.dy * o.dy);
+    o.sx = px - tau * dxn;
+    o.sy = py - tau * dyn;
+    return o;
+}
+// walk_step_exact with interp2_general, sqrt_core and div_core (same bits where walk_odd is false,
+// set in `odd`)
+__device__ __forceinline__ WalkStep walk_step_core(const double2& g00, const double2& g01, const double2& g10,
+                                                   const double2& g11, double fa, double fb, double px, double py,
+                                                   double tau, bool& odd) {
+    WalkStep o;
+    o.dx = interp2_general(fa, fb, g00.x, g01.x, g10.x, g11.x);
+    o.dy = interp2_general(fa, fb, g00.y, g01.y, g10.y, g11.y);
+    const double s1 = o.dx * o.dx + o.dy * o.dy;
+    const double nrm = sqrt_core(s1);
+    const double dxn = div_core(o.dx, nrm);
+    // both divisors computed, selected bitwise (a ?: here becomes a branch on the chain)
+    const double r2 = sqrt_core(dxn * dxn + o.dy * o.dy);
+    const long long small = -(long long)(nrm < 0.01);
+    const double den = __longlong_as_double((__double_as_longlong(nrm) & small) | (__double_as_longlong(r2) & ~small));
+    const double dyn = div_core(o.dy, den);
+    o.sx = px - tau * dxn;
+    o.sy = py - tau * dyn;
+    odd = walk_odd(o.dx, o.dy, s1);
+    return o;
+}
+// walk_step_core with the divisions taken from the square roots' reciprocals (div_rs): the step's
+// dependent f64 chain 45 -> 33 operations (loop form 3 and the obstacle-safe walker's run loop).  The
+// same bits wherever `odd` comes back false, which eik_selftest_walker_math vouches for (counts[2],
+// counts[4]).
+__device__ __forceinline__ WalkStep walk_step_rs(const double2& g00, const double2& g01, const double2& g10,
+                                                 const double2& g11, double fa, double fb, double px, double py,
+                                                 double tau, bool& odd) {
+    WalkStep o;
+    o.dx = interp2_general(fa, fb, g00.x, g01.x, g10.x, g11.x);
+    o.dy = interp2_general(fa, fb, g00.y, g01.y, g10.y, g11.y);
+    const double s1 = o.dx * o.dx + o.dy * o.dy;
+    double h1, h2;
+    const double nrm = sqrt_core_h(s1, h1);
+    const double dxn = div_rs(o.dx, nrm, h1);
+    const double r2 = sqrt_core_h(dxn * dxn + o.dy * o.dy, h2);
+    const long long small = -(long long)(nrm < 0.01);
+    const double den = __longlong_as_double((__double_as_longlong(nrm) & small) | (__double_as_longlong(r2) & ~small));
+    const double hd = __longlong_as_double((__double_as_longlong(h1) & small) | (__double_as_longlong(h2) & ~small));
+    const double dyn = div_rs(o.dy, den, hd);
+    o.sx = px - tau * dxn;
+    o.sy = py - tau * dyn;
+    odd = walk_odd(o.dx, o.dy, s1);
+    return o;
+}
+
 // DPP quad_perm moves of a double, the 2D walker's lane-pair form: Q = 0xB1 [1, 0, 3, 2] the
 // partner lane's value (lane ^ 1), 0xA0 [0, 0, 2, 2] the even lane's, 0xF5 [1, 1, 3, 3] the odd one's
 template <int Q>
@@ -272,10 +341,12 @@ __device__ void build_window(PathLds& s, const R* __restrict__ T, int64_t H, int
     }
 }
 
-template <typename R, bool BLOCK = false>
-__device__ void path_builder(PathLds& s, const R* __restrict__ T, int64_t H, int64_t W) {
-    const int wv = (int)(threadIdx.x >> 6);
-    const int w = wv - 1;  // builder index 0 .. kBuilders - 1
+// A builder wave's life, the 2D and the 3D walkers' (LDS = PathLds or gdm.hip's Path3Lds): poll
+// req_seq, run build(w) -- w the builder's index, wave - 1 -- for each new request, publish it in
+// `done`; leave on the walker's quit (-1), or when no request came for kPathSpin.
+template <typename LDS, typename F>
+__device__ __forceinline__ void builder_loop(LDS& s, F&& build) {
+    const int w = (int)(threadIdx.x >> 6) - 1;
     int seen = 0;
     unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     for (;;) {
@@ -287,12 +358,98 @@ __device__ void path_builder(PathLds& s, const R* __restrict__ T, int64_t H, int
             continue;
         }
         seen = q;
-        build_window<R, BLOCK>(s, T, H, W, s.req_b, s.req_x0, s.req_y0, w);
+        build(w);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(&s.done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         t0 = __builtin_amdgcn_s_memrealtime();
     }
 }
+
+template <typename R, bool BLOCK = false>
+__device__ void path_builder(PathLds& s, const R* __restrict__ T, int64_t H, int64_t W) {
+    builder_loop(s, [&](int w) { build_window<R, BLOCK>(s, T, H, W, s.req_b, s.req_x0, s.req_y0, w); });
+}
+
+// The walker's window state, the 2D counterpart of gdm.hip's Win3: which buffer holds which
+// window, the request in flight and the fast bounds of the step.
+struct Walk2Win {
+    PathLds& s;
+    const int64_t H, W;
+    // window origins of the two buffers (scalars, not an indexed array: no private->LDS promotion)
+    int64_t wx0 = -((int64_t)1 << 40), wx1 = wx0, wy0 = wx0, wy1 = wx0;
+    int cur = 0, seq = 0;
+    bool pending = false;
+    const int64_t xmax, ymax;
+    // Fast path: while lo_x <= i <= hi_x and lo_y <= j <= hi_y nothing has to happen this step
+    // (the corners lie in the current window and, unless a build is pending, not within
+    // kPrefetch of an inner edge) -- four int32 compares on the step's dependency chain instead
+    // of the window bookkeeping, which runs only when the bounds are crossed.
+    int lo_x = 1, hi_x = 0, lo_y = 1, hi_y = 0;  // empty: the first step takes the slow path
+    int cx0i = 0, cy0i = 0;                     // current window origin
+    __device__ __forceinline__ Walk2Win(PathLds& lds, int64_t h, int64_t w)
+        : s(lds), H(h), W(w), xmax(w > kPW ? w - kPW : 0), ymax(h > kPW ? h - kPW : 0) {}
+    __device__ __forceinline__ void issue(int b, int64_t i, int64_t j) {  // build the window centred on (i, j) into b
+        int64_t x0 = i - kPW / 2, y0 = j - kPW / 2;
+        x0 = x0 > xmax ? xmax : x0 < 0 ? 0 : x0;
+        y0 = y0 > ymax ? ymax : y0 < 0 ? 0 : y0;
+        if (b) { wx1 = x0; wy1 = y0; } else { wx0 = x0; wy0 = y0; }
+        s.req_x0 = x0;
+        s.req_y0 = y0;
+        s.req_b = b;
+        __hip_atomic_store(&s.req_seq, ++seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    __device__ __forceinline__ bool wait_built() {
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (__hip_atomic_load(&s.done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < seq * kBuilders) {
+            if (__builtin_amdgcn_s_memrealtime() - t0 > kPathSpin) return false;
+            __builtin_amdgcn_s_sleep(1);
+        }
+        return true;
+    }
+    __device__ __forceinline__ bool inside(int b, int64_t i, int64_t j) const {
+        const int64_t x0 = b ? wx1 : wx0, y0 = b ? wy1 : wy0;
+        return i >= x0 && j >= y0 && i + 1 < x0 + kPW && j + 1 < y0 + kPW;
+    }
+    __device__ __forceinline__ void set_bounds() {
+        const int64_t x0 = cur ? wx1 : wx0, y0 = cur ? wy1 : wy0;
+        cx0i = (int)x0;
+        cy0i = (int)y0;
+        lo_x = cx0i + (!pending && x0 > 0 ? kPrefetch : 0);
+        hi_x = cx0i + kPW - 2 - (!pending && x0 < xmax ? kPrefetch : 0);
+        lo_y = cy0i + (!pending && y0 > 0 ? kPrefetch : 0);
+        hi_y = cy0i + kPW - 2 - (!pending && y0 < ymax ? kPrefetch : 0);
+        hi_x = hi_x < (int)W - 2 ? hi_x : (int)W - 2;  // inside the bounds implies i + 1 < W, j + 1 < H
+        hi_y = hi_y < (int)H - 2 ? hi_y : (int)H - 2;
+    }
+    // The cell (i, j) of a point in the raster (i + 1 < W, j + 1 < H) left the fast bounds: switch
+    // to the window that holds its corners (waiting only if the build is still running, or the
+    // walk turned away from the prefetched window), prefetch when it is within kPrefetch of an
+    // inner edge, set the bounds anew.  false: a build never finished.
+    __device__ __forceinline__ bool cross(int64_t i, int64_t j) {
+        if (!inside(cur, i, j)) {  // the 2 x 2 interpolation corners left the window
+            const int nb = seq == 0 ? 0 : 1 - cur;
+            bool have = false;
+            if (pending) {
+                pending = false;
+                if (!wait_built()) return false;
+                have = inside(nb, i, j);
+            }
+            if (!have) {
+                issue(nb, i, j);
+                if (!wait_built()) return false;
+            }
+            cur = nb;
+        }
+        const int64_t cx0 = cur ? wx1 : wx0, cy0 = cur ? wy1 : wy0;
+        if (!pending && ((i - cx0 < kPrefetch && cx0 > 0) || (cx0 + kPW - 2 - i < kPrefetch && cx0 < xmax) ||
+                         (j - cy0 < kPrefetch && cy0 > 0) || (cy0 + kPW - 2 - j < kPrefetch && cy0 < ymax))) {
+            issue(1 - cur, i, j);
+            pending = true;
+        }
+        set_bounds();
+        return true;
+    }
+};
 
 // One path's walk by one workgroup.  ONE kernel template for the single-path launch (A = Gdm2dArgs,
 // one workgroup) and the grid form (A = GdmBatchArgs: workgroup p takes descriptor p -- its map,

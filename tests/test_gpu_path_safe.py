@@ -213,6 +213,62 @@ def test_drop_in(ctx):
         FM.getPathSafe(T, (31.0, 30.0), goals[0], 0.5)  # starts on the block
 
 
+def _window_switches(pts, H, W):
+    """The walkers' window rule (csrc/gdm_walk.hpp Walk2Win::cross) on the points a step starts from:
+    per switch of the 64-node window, the axis along which the point's cell left it."""
+    PW, PRE = 64, 16
+    xmax, ymax = max(W - PW, 0), max(H - PW, 0)
+
+    def origin(i, j):
+        return min(max(i - PW // 2, 0), xmax), min(max(j - PW // 2, 0), ymax)
+
+    def inside(w, i, j):
+        return w is not None and w[0] <= i and i + 1 < w[0] + PW and w[1] <= j and j + 1 < w[1] + PW
+
+    cur = ahead = None
+    axes = []
+    for x, y in pts:
+        i, j = int(x), int(y)
+        if not inside(cur, i, j):
+            if cur is not None:
+                axes.append("y" if cur[0] <= i < cur[0] + PW - 1 else "x")
+            cur = ahead if inside(ahead, i, j) else origin(i, j)
+            ahead = None
+        if ahead is None and ((i - cur[0] < PRE and cur[0] > 0) or (cur[0] + PW - 2 - i < PRE and cur[0] < xmax) or
+                              (j - cur[1] < PRE and cur[1] > 0) or (cur[1] + PW - 2 - j < PRE and cur[1] < ymax)):
+            ahead = origin(i, j)
+    return axes
+
+
+def test_safe_walk_is_the_default_walk_without_obstacles(ctx):
+    """The two walkers run one copy of the window state and of the step's arithmetic: on a smooth finite
+    field without obstacles, across several window switches in both axes, eik_path2d_safe_f64's rows are
+    eik_path2d_f64's bit for bit (loop forms 0 and 4), with the same n and status, and no fallback."""
+    from eikonal import _lib as L
+
+    H, W, tau = 200, 160, 0.5
+    start, goal = (150.25, 190.5), (8, 8)
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    T = np.sqrt((x - goal[0]) ** 2 + 3.0 * (y - goal[1]) ** 2) + 0.5 * np.sin(x / 9.0) * np.sin(y / 11.0)
+    assert np.isfinite(T).all()
+    # the precondition, on the host: a plain gradient walk (the rule's restatement takes no fallback, drops
+    # nothing, never stalls, ends at the goal) that switches windows along x and along y
+    ref, rst, rinfo = S.safe_path(T, start, goal, tau)
+    assert rst == S.DONE and rinfo[0] == 0 and rinfo[1] == 0 and rinfo[2] == -1, (rst, rinfo)
+    axes = _window_switches(ref[:-2], H, W)  # (the last walked point and the appended goal start no step)
+    assert len(axes) >= 3 and "x" in axes and "y" in axes, axes
+    safe, sst, info = ctx.path2d_safe(T, start, goal, tau)
+    assert sst == S.DONE and np.array_equal(info, [0, 0, -1, rinfo[3]]), (sst, info, rinfo)
+    try:
+        for form in (0, 4):
+            ctx.set_option(L.OPT_PATH_LOOP, form)
+            p, st = ctx.path2d(T, start, goal, tau)
+            assert st == sst and p.shape == safe.shape, (form, st, sst, p.shape, safe.shape)
+            assert np.array_equal(p.view(np.uint64), safe.view(np.uint64)), (form, np.abs(p - safe).max())
+    finally:
+        ctx.set_option(L.OPT_PATH_LOOP, 4)  # the default (include/eikonal.h)
+
+
 @pytest.mark.parametrize("name", ["A", "B"])
 def test_default_mode_untouched(ctx, fields, name):
     """eik_path2d_f64 on the same fields is still oracle.gdm2d's walk, truncation included"""
