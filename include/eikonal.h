@@ -44,13 +44,20 @@ typedef enum { EIK_F32 = 0, EIK_F64 = 1 } eik_dtype;
 
 /* path status (eik_path2d / eik_path3d), mirrors the reference's exits */
 typedef enum {
-    EIK_PATH_DONE = 0,     /* stop radius (< 1.5 cells) or step budget hit; end appended (:231-234) */
+    EIK_PATH_DONE = 0,     /* stop radius (< 1.5 cells) or step budget hit; end appended (:231-234):
+                              always with n_out <= cap, `end` being row n_out - 1                */
     EIK_PATH_FALLBACK = 1, /* NaN gradient: the reference's fallback returns a truncated path
                               (numpy-2 behaviour of FastMarching.py:178-218)                       */
     EIK_PATH_ERROR = 2,    /* the reference raises out of getPathGDM: a NaN point, an index out of
-                              range (3D: also a coordinate <= -1, which numpy's uint32 cast turns
-                              into an index past every axis), int(round()) of a NaN or infinite
-                              coordinate in the NaN branch; the path as it stands is returned      */
+                              range (also a coordinate <= -1, which numpy's uint32 cast turns
+                              into an index past every axis, and any coordinate >= 2^31; 2D: also
+                              an infinite coordinate at the top of a step, computeGradient's
+                              int(point)), 3D: int(round()) of a NaN or infinite coordinate in the
+                              NaN branch; the path as it stands is returned.  A coordinate in
+                              (-1, 0) is cell 0 with a negative fraction and walks on.
+                              Also: out of point budget -- the walk has no row left for its next
+                              point or, after the stop radius or the last step, for `end`:
+                              n_out == cap, the first cap rows of the walk                        */
     EIK_PATH_STUCK = 3     /* eik_path2d_safe_* only: no lower neighbour to descend to, or the
                               iteration budget ran out short of the stop radius; end NOT appended   */
 } eik_path_status;

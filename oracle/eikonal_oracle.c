@@ -15,7 +15,7 @@
  *   computeTmap       FastMarching.py:92-112     -> orc_fmm2d()  (intended semantics: the
  *                                                   reference raises at :107)
  *   biComputeTmap     FastMarching.py:114-162    -> orc_fmm2d_bidir()
- *   getPathGDM        FastMarching.py:164-236    -> orc_gdm2d()
+ *   getPathGDM        FastMarching.py:164-236    -> orc_gdm2d(), orc_gdm2d_events()
  *   computeGradient   FastMarching.py:242-300    -> grad_at(), orc_gradient2d()
  *   interpolatePoint  FastMarching.py:305-338    -> interp2()
  *   FM3D updateNode   FastMarching3D.py:19-101   -> update3d()
@@ -283,7 +283,13 @@ int orc_fmm2d_bidir(const double *cost, int64_t H, int64_t W, int64_t gx, int64_
 static inline double TT(const double *T, int64_t W, int64_t j, int64_t i) { return T[j * W + i]; }
 
 /* computeGradient body for one (j, i), FastMarching.py:262-297 */
-static void grad_at(const double *T, int64_t m, int64_t n, int64_t j, int64_t i, double *gnx, double *gny) {
+/* sq2: `x**2` of a numpy float64 scalar (:221-227, :296-297): libm pow as the reference has it, or
+ * -- exact != 0, the conditioning check of tests/test_walk2d_cases.py -- the exact product the GPU
+ * walker uses. */
+static inline double sq2(double x, int exact) { return exact ? x * x : pow(x, 2); }
+
+static void grad_at_sq(const double *T, int64_t m, int64_t n, int64_t j, int64_t i, double *gnx, double *gny,
+                       int exact) {
     double gy, gx;
     if (j == 0)
         gy = TT(T, n, 1, i) - TT(T, n, 0, i);
@@ -304,8 +310,11 @@ static void grad_at(const double *T, int64_t m, int64_t n, int64_t j, int64_t i,
         gx = isinf(TT(T, n, j, i - 1)) ? TT(T, n, j, i + 1) - TT(T, n, j, i)
                                        : (TT(T, n, j, i + 1) - TT(T, n, j, i - 1)) / 2;
     /* :296-297  Gx[j,i]**2 on a numpy scalar -> libm pow */
-    *gnx = gx / sqrt(pow(gx, 2) + pow(gy, 2));
-    *gny = gy / sqrt(pow(gx, 2) + pow(gy, 2));
+    *gnx = gx / sqrt(sq2(gx, exact) + sq2(gy, exact));
+    *gny = gy / sqrt(sq2(gx, exact) + sq2(gy, exact));
+}
+static void grad_at(const double *T, int64_t m, int64_t n, int64_t j, int64_t i, double *gnx, double *gny) {
+    grad_at_sq(T, m, n, j, i, gnx, gny, 0);
 }
 
 /* computeGradient(cost, point) FastMarching.py:242-300.  has_point=0 -> whole field. */
@@ -356,10 +365,49 @@ double orc_interp2(double px, double py, const double *M, int64_t m, int64_t n, 
 
 static inline double norm2(double a, double b) { return sqrt(a * a + b * b); }
 
+/* The cell index of one coordinate at the top of a 2D step: computeGradient's int(point) (:250,
+ * outside getPathGDM's try) and then interpolatePoint's np.uint32(np.fix(p)) (:306-307), made
+ * total.  NaN raises ValueError and +-inf OverflowError at :250 (both ORC_REF_VALUEERROR); numpy on
+ * x86-64 turns p <= -1 into 2^32 - |fix(p)|, past every axis, so mapI[j,i] (:323) raises IndexError;
+ * p >= 2^31 is an IndexError here as well (numpy wraps modulo 2^32 from 2^32 on: not reproduced, as
+ * fix_index).  -1 < p < 0 gives index 0 and a negative fraction.  The cast only sees (-1, 2^31). */
+static int fix_index2(double p, int64_t *idx) {
+    *idx = 0;
+    if (!isfinite(p)) return ORC_REF_VALUEERROR;
+    if (p <= -1.0 || p >= 2147483648.0) return ORC_REF_INDEXERROR;
+    *idx = (int64_t)p;
+    return 0;
+}
+
+/* exit kinds of the 2D walk, ev[9] */
+#define GDM2_EXIT_STOP 0         /* stop radius (:231-232)                                        */
+#define GDM2_EXIT_BUDGET 1       /* round(15000/tau) steps taken                                   */
+#define GDM2_EXIT_FB_NODE 2      /* NaN fallback: node appended, OverflowError at :197 caught      */
+#define GDM2_EXIT_FB_EMPTY 3     /* NaN fallback: every point popped, gamma[-1] IndexError caught  */
+#define GDM2_EXIT_FB_OFF 4       /* NaN fallback: the node is off the raster, IndexError caught    */
+#define GDM2_EXIT_NONFINITE 5    /* a NaN or infinite coordinate at the top of a step (:250)       */
+#define GDM2_EXIT_INDEX 6        /* a coordinate <= -1 or in the last cell or past it (:323)       */
+#define GDM2_NEV 12
+
 /* getPathGDM FastMarching.py:164-236 (numpy-2 semantics of the NaN fallback).
- * out: (max_out x 2) row-major; *n_out rows written; *status GDM_*. */
-int orc_gdm2d(const double *T, int64_t H, int64_t W, double ix, double iy, double ex, double ey, double tau,
-              double *out, int64_t max_out, int64_t *n_out, int *status) {
+ * out: (max_out x 2) row-major; *n_out rows written; *status GDM_*.  exact: sq2's switch.  max_steps
+ * > 0: a step budget below the reference's round(15000/tau) (the rows a walk holds when a point
+ * budget of max_steps + 1 rows runs out; the GPU entries' `cap`).  ev (may be
+ * NULL) counts what the walk did, so that a test can tell which branches a crafted field takes:
+ *   ev[0] steps taken (points appended at :224/:229)   ev[5] points with a coordinate in (-1, 0)
+ *   ev[1] steps on the |g| < 0.01 branch (:220-224)    ev[6] fallback pops on +inf nodes (:182-185)
+ *   ev[2] steps interpolated with a == 0, b != 0       ev[7] fallback pops within 1 of the node (:188)
+ *   ev[3] ... with b == 0, a != 0                      ev[8] fallback node reads whose index wrapped
+ *   ev[4] ... with a == 0 and b == 0                   ev[9] exit kind (GDM2_EXIT_*)
+ *   ev[10] the most rows the path held at any time
+ *   ev[11] steps whose interpolated gradient is outside the domain of the GPU walker's fast step
+ *          (gdm_walk.hpp walk_odd: |g|^2 not in [2^-767, 2^200], or a nonzero component below 2^-900) */
+int orc_gdm2d_events(const double *T, int64_t H, int64_t W, double ix, double iy, double ex, double ey, double tau,
+                     double *out, int64_t max_out, int64_t *n_out, int *status, int exact, int64_t max_steps,
+                     int64_t *ev) {
+    int64_t ev_local[GDM2_NEV];
+    if (!ev) ev = ev_local;
+    memset(ev, 0, GDM2_NEV * sizeof *ev);
     if (!T || !out || !n_out || !status || H < 3 || W < 3 || max_out < 2 || !(tau > 0)) return ORC_ERR_ARG;
     int64_t n = 0;
 #define PUSH(X, Y)                                  \
@@ -368,37 +416,54 @@ int orc_gdm2d(const double *T, int64_t H, int64_t W, double ix, double iy, doubl
         out[2 * n] = (X);                           \
         out[2 * n + 1] = (Y);                       \
         ++n;                                        \
+        if (n > ev[10]) ev[10] = n;                 \
     } while (0)
+#define LEAVE(ST, KIND, RC)  \
+    do {                     \
+        *status = (ST);      \
+        ev[9] = (KIND);      \
+        *n_out = n;          \
+        return (RC);         \
+    } while (0)
+    *n_out = 0;
+    *status = GDM_ERROR;
     PUSH(ix, iy); /* :168-169 */
-    long steps = (long)nearbyint(15000.0 / tau); /* round(15000/tau), half-even */
+    double dsteps = nearbyint(15000.0 / tau); /* round(15000/tau), half-even */
+    long steps = dsteps < 4e18 ? (long)dsteps : (long)4e18;
+    if (max_steps > 0 && max_steps < steps) steps = (long)max_steps;
     *status = GDM_DONE;
+    ev[9] = GDM2_EXIT_BUDGET;
     for (long k = 0; k < steps; ++k) { /* :173 */
         double px = out[2 * (n - 1)], py = out[2 * (n - 1) + 1];
-        /* computeGradient's int(point) raises ValueError on NaN (:250, outside the try) */
-        if (isnan(px) || isnan(py)) { *status = GDM_ERROR; *n_out = n; return ORC_REF_VALUEERROR; }
-        uint32_t i = (uint32_t)trunc(px), j = (uint32_t)trunc(py);
+        int64_t i, j;
+        /* computeGradient's int(point) (:250-252, outside the try): point[1] first, then point[0] */
+        if (!isfinite(py) || !isfinite(px)) LEAVE(GDM_ERROR, GDM2_EXIT_NONFINITE, ORC_REF_VALUEERROR);
+        if (fix_index2(px, &i) || fix_index2(py, &j) || i + 1 >= W || j + 1 >= H) /* interpolatePoint IndexError */
+            LEAVE(GDM_ERROR, GDM2_EXIT_INDEX, ORC_REF_INDEXERROR);
+        if ((px > -1.0 && px < 0.0) || (py > -1.0 && py < 0.0)) ++ev[5];
         double dx, dy;
-        if (i + 1 >= (uint32_t)W || j + 1 >= (uint32_t)H) { /* interpolatePoint IndexError */
-            *status = GDM_ERROR;
-            *n_out = n;
-            return ORC_REF_INDEXERROR;
-        } else {
+        {
             double gx[2][2], gy[2][2];
             for (int jj = 0; jj < 2; ++jj)
-                for (int ii = 0; ii < 2; ++ii) grad_at(T, H, W, j + jj, i + ii, &gx[jj][ii], &gy[jj][ii]);
-            double a = px - i, b = py - j;
+                for (int ii = 0; ii < 2; ++ii) grad_at_sq(T, H, W, j + jj, i + ii, &gx[jj][ii], &gy[jj][ii], exact);
+            double a = px - (double)i, b = py - (double)j;
+            if (a == 0 && b == 0) ++ev[4];
+            else if (a == 0) ++ev[2];
+            else if (b == 0) ++ev[3];
             dx = interp2_patch(a, b, gx); /* :175 */
             dy = interp2_patch(a, b, gy); /* :176 */
         }
         if (isnan(dx) || isnan(dy)) { /* :178-218 */
-            /* try: */
+            /* try: (the point is finite and in (-1, W - 1) x (-1, H - 1): the conversions are exact) */
             int64_t nx = (int64_t)nearbyint(px), ny = (int64_t)nearbyint(py); /* :180-181 */
             for (;;) { /* :182-185 */
                 int64_t wx = nx < 0 ? nx + W : nx, wy = ny < 0 ? ny + H : ny; /* python wrap */
-                if (wx < 0 || wy < 0 || wx >= W || wy >= H) { *status = GDM_FALLBACK; *n_out = n; return ORC_OK; }
+                if (wx < 0 || wy < 0 || wx >= W || wy >= H) LEAVE(GDM_FALLBACK, GDM2_EXIT_FB_OFF, ORC_OK);
+                if (nx < 0 || ny < 0) ++ev[8];
                 if (!isinf(T[wy * W + wx])) break;
                 --n; /* np.delete(gamma, -1) */
-                if (n == 0) { *status = GDM_FALLBACK; *n_out = 0; return ORC_OK; } /* gamma[-1] IndexError */
+                ++ev[6];
+                if (n == 0) LEAVE(GDM_FALLBACK, GDM2_EXIT_FB_EMPTY, ORC_OK); /* gamma[-1] IndexError */
                 double qx = out[2 * (n - 1)], qy = out[2 * (n - 1) + 1];
                 nx = (int64_t)nearbyint(qx);
                 ny = (int64_t)nearbyint(qy);
@@ -406,35 +471,48 @@ int orc_gdm2d(const double *T, int64_t H, int64_t W, double ix, double iy, doubl
             if (n > 0) { /* :187-191 */
                 while (norm2(out[2 * (n - 1)] - (double)nx, out[2 * (n - 1) + 1] - (double)ny) < 1) {
                     --n;
+                    ++ev[7];
                     if (n == 0) break;
                 }
             }
             PUSH((double)nx, (double)ny); /* :193 */
             /* :194-197  np.uint32(nearN + [0,-1]) is a list concatenation with a -1 in it:
              * numpy 2 raises OverflowError, the bare except at :217 returns gamma. */
-            *status = GDM_FALLBACK;
-            *n_out = n;
-            return ORC_OK;
+            LEAVE(GDM_FALLBACK, GDM2_EXIT_FB_NODE, ORC_OK);
+        }
+        {
+            double s1 = dx * dx + dy * dy;
+            if (!(s1 >= 0x1p-767 && s1 <= 0x1p200) || (dx != 0.0 && fabs(dx) < 0x1p-900) ||
+                (dy != 0.0 && fabs(dy) < 0x1p-900))
+                ++ev[11];
         }
         double sx_, sy_;
         if (norm2(dx, dy) < 0.01) { /* :220-224 */
-            double dnx = dx / sqrt(pow(dx, 2) + pow(dy, 2));
-            double dny = dy / sqrt(pow(dx, 2) + pow(dy, 2));
+            double dnx = dx / sqrt(sq2(dx, exact) + sq2(dy, exact));
+            double dny = dy / sqrt(sq2(dx, exact) + sq2(dy, exact));
             sx_ = px - tau * dnx;
             sy_ = py - tau * dny;
+            ++ev[1];
         } else { /* :225-229 -- dy normalised with the already-normalised dx */
-            dx = dx / sqrt(pow(dx, 2) + pow(dy, 2));
-            dy = dy / sqrt(pow(dx, 2) + pow(dy, 2));
+            dx = dx / sqrt(sq2(dx, exact) + sq2(dy, exact));
+            dy = dy / sqrt(sq2(dx, exact) + sq2(dy, exact));
             sx_ = px - tau * dx;
             sy_ = py - tau * dy;
         }
+        ++ev[0];
         PUSH(sx_, sy_);
-        if (norm2(sx_ - ex, sy_ - ey) < 1.5) break; /* :231-232 */
+        if (norm2(sx_ - ex, sy_ - ey) < 1.5) { ev[9] = GDM2_EXIT_STOP; break; } /* :231-232 */
     }
     PUSH(ex, ey); /* :234 */
     *n_out = n;
     return ORC_OK;
 #undef PUSH
+#undef LEAVE
+}
+
+int orc_gdm2d(const double *T, int64_t H, int64_t W, double ix, double iy, double ex, double ey, double tau,
+              double *out, int64_t max_out, int64_t *n_out, int *status) {
+    return orc_gdm2d_events(T, H, W, ix, iy, ex, ey, tau, out, max_out, n_out, status, 0, 0, NULL);
 }
 
 /* ---------------------------------------------------------------------------- 3D FMM */

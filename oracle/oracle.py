@@ -47,6 +47,7 @@ def lib():
         L.orc_interp3.restype = C.c_double
         L.orc_interp3.argtypes = [C.c_double] * 3 + [_dp, i64, i64, i64, C.POINTER(C.c_int)]
         L.orc_gdm2d.argtypes = [_dp, i64, i64] + [C.c_double] * 5 + [_dp, i64, C.POINTER(i64), C.POINTER(C.c_int)]
+        L.orc_gdm2d_events.argtypes = L.orc_gdm2d.argtypes + [C.c_int, i64, _ip]
         L.orc_fmm3d.argtypes = [_dp, i64, i64, i64, _ip, C.c_void_p, _dp]
         L.orc_fmm3d_trace.argtypes = [_dp, i64, i64, i64, _ip, C.c_void_p, _dp, _ip]
         L.orc_gdm3d.argtypes = [_dp, i64, i64, i64, _dp, _dp, C.c_double, _dp, i64, C.POINTER(i64),
@@ -137,18 +138,31 @@ def interp3(point, M):
     return v
 
 
-def gdm2d(T, init, end, tau=0.5, max_out=None):
-    """getPathGDM FastMarching.py:164-236 -> (path (K,2), status)."""
+GDM2D_EVENTS = ("steps", "unit_steps", "a_zero", "b_zero", "ab_zero", "negative_cell_points", "inf_pops",
+                "near_pops", "wrapped_reads", "exit", "peak_rows", "odd_steps")
+# GDM2D_EVENTS["exit"]: how the walk ended (GDM2_EXIT_* of eikonal_oracle.c)
+EXIT_STOP, EXIT_BUDGET, EXIT_FB_NODE, EXIT_FB_EMPTY, EXIT_FB_OFF, EXIT_NONFINITE, EXIT_INDEX = range(7)
+
+
+def gdm2d(T, init, end, tau=0.5, max_out=None, events=False, exact=False, max_steps=0):
+    """getPathGDM FastMarching.py:164-236 -> (path (K,2), status), with events=True also the walk's
+    event counts as a dict keyed by GDM2D_EVENTS (orc_gdm2d_events).  exact=True squares with exact
+    products where the reference's scalar `x**2` goes through libm pow (the GPU walker's arithmetic);
+    max_steps > 0 is a step budget below round(15000 / tau) (what a point budget of max_steps + 1 rows
+    leaves of the walk)."""
     T = _f64(T)
     H, W = T.shape
     steps = int(round(15000 / tau))
-    max_out = max_out or steps + 4
+    max_out = max_out or (min(steps, max_steps) if max_steps > 0 else steps) + 4
     out = np.empty((max_out, 2))
     n, st = i64(0), C.c_int(0)
-    rc = lib().orc_gdm2d(T, H, W, float(init[0]), float(init[1]), float(end[0]), float(end[1]), float(tau),
-                         out, max_out, C.byref(n), C.byref(st))
+    ev = np.zeros(len(GDM2D_EVENTS), np.int64)
+    rc = lib().orc_gdm2d_events(T, H, W, float(init[0]), float(init[1]), float(end[0]), float(end[1]), float(tau),
+                                out, max_out, C.byref(n), C.byref(st), 1 if exact else 0, int(max_steps), ev)
     if rc not in (OK,) and st.value != GDM_ERROR:
         _chk(rc)
+    if events:
+        return out[: n.value].copy(), st.value, dict(zip(GDM2D_EVENTS, ev.tolist()))
     return out[: n.value].copy(), st.value
 
 

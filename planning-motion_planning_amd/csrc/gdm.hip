@@ -38,6 +38,21 @@ namespace eik {
 #endif
 
 
+// (uint32_t)trunc(x) as ONE defined conversion: the hardware truncates and CLAMPS to the type's range
+// (x <= -1, NaN and -inf -> 0; x >= 2^32 and +inf -> 2^32 - 1), where a C++ cast of such a value is
+// undefined.  The result is the reference's np.uint32(np.fix(p)) only for p in (-1, 2^31); both
+// walkers decide every other coordinate themselves.
+__device__ __forceinline__ uint32_t cvt_u32(double x) {
+    uint32_t r;
+    asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+// the 2D walker's: every lane holds the same point, so the cell index is wave-uniform -- read into a
+// scalar register, the branches on it stay scalar branches
+__device__ __forceinline__ uint32_t cell_u32(double x) {
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)cvt_u32(x));
+}
+
 template <typename R, int LOOP, typename A = Gdm2dArgs>
 __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
     const Gdm2dArgs a = path_args<R>(arg);
@@ -66,14 +81,30 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
     int64_t n = 1;
     const double tau = a.tau;
     Walk2Win win(s, H, W);
-    // Window bookkeeping of a step whose cell (i, j) left the fast bounds: errors (NaN point, out
-    // of range, a build that never finished) set status and return false; else the corners are in
-    // window `win.cur` afterwards.
+    // Window bookkeeping of a step whose cell (i, j) = cell_u32 of (px, py) left the fast bounds -- and
+    // the coordinate-to-index rule of DESIGN 3.4b, which every point outside the fast bounds passes
+    // here before anything is indexed with (i, j): the clamped conversions are the reference's
+    // np.uint32(np.fix(p)) only for p in (-1, 2^31).  A NaN or infinite coordinate raises at
+    // computeGradient's int(point) (:250), p <= -1 (numpy: index 2^32 - |fix(p)|), W - 1 <= p and
+    // p >= 2^31 (not wrapped modulo 2^32) are the IndexError of :323: status ERROR, false.  The
+    // range test is in 64 bits (i + 1 of i = 2^32 - 1 does not wrap).  A point in (-1, 0) has cell 0
+    // and a negative fraction and walks on.  false as well when a build never finished; else the
+    // corners are in window `win.cur` afterwards.
     auto slow_step = [&](uint32_t i, uint32_t j) -> bool {
-        if (__builtin_isnan(px) || __builtin_isnan(py)) { status = kGdmError; return false; }
-        if (i + 1 >= (uint64_t)W || j + 1 >= (uint64_t)H) { status = kGdmError; return false; }
-        if (!win.cross(i, j)) { status = kGdmError; return false; }
+        if (!(__builtin_isfinite(px) && __builtin_isfinite(py))) { status = kGdmError; return false; }
+        if (px <= -1.0 || py <= -1.0 || ((i | j) >> 31) != 0u || (int64_t)i + 1 >= W || (int64_t)j + 1 >= H) {
+            status = kGdmError;
+            return false;
+        }
+        if (!win.cross((int64_t)i, (int64_t)j)) { status = kGdmError; return false; }
         return true;
+    };
+    // forms 0-3: the fast bounds as integer tests on the conversions' results.  Cell 0 of either
+    // axis is never inside them -- p <= -1, NaN and -inf convert to 0 as a point of cell 0 does --
+    // and +inf and p >= 2^31 convert to a negative int: all of them take slow_step.
+    auto fast_cell = [&](uint32_t i, uint32_t j) -> bool {
+        const int lx = win.lo_x > 1 ? win.lo_x : 1, ly = win.lo_y > 1 ? win.lo_y : 1;
+        return (int)i >= lx && (int)i <= win.hi_x && (int)j >= ly && (int)j <= win.hi_y;
     };
     // NaN fallback (:178-218) as the reference behaves under numpy 2: the neighbour probe
     // `np.uint32(nearN + [0,-1])` raises OverflowError, caught at :217.  Lane 0 edits the path.
@@ -149,12 +180,16 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
                 const unsigned c0 = (unsigned)(yl ? win.cy0i : win.cx0i) * sc;
                 const char* const base = reinterpret_cast<const char*>(s.g[win.cur]) + (yl ? sizeof(double) : 0);
                 int kk = 0;
-                // One conditional branch per step: the point is stored and the state advanced before
-                // the exit test (the stores are in range -- n < cap -- and a step the handler below
-                // redoes stores its point at the same index), and the exit undoes the advance.
+                // One conditional branch per step: the state is advanced before the exit test and the
+                // exit undoes the advance.  Each pass stores the point it starts from, row n - 1 (the
+                // first pass rewrites the row with the bits it holds): the point of a step that
+                // leaves -- computed from corners outside the window, or of a step that ends in an
+                // error or the NaN fallback -- is never stored, so nothing is written past the
+                // rows returned.
                 double pp = p;
                 bool leave;
                 do {
+                    outl[2 * (n - 1)] = p;  // every lane: its component's address
                     // (one v_cvt_u32_f64 on p, the corner as (double)u beside it: no difference,
                     // profiles/r05k_walker_ab.log P4_CVT=1)
                     const double t = __builtin_trunc(p);
@@ -185,7 +220,6 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
                     // (a NaN d makes s1 NaN: odd)
                     const bool oddl = !(s1 >= 0x1p-767 && s1 <= 0x1p200) | ((d != 0.0) & (__builtin_fabs(d) < 0x1p-900));
                     const bool bad = __builtin_amdgcn_ballot_w64(oddl) != 0ull;
-                    outl[2 * n] = pn;  // every lane: its component's address
                     leave = (int)!in | (int)bad | (int)(kk >= left);
                     ++n;
                     pp = p;
@@ -200,8 +234,8 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
                 // read into scalar registers, so the handler stays wave-uniform code
                 px = readlane_f64(p, 0);
                 py = readlane_f64(p, 1);
-                i = (uint32_t)__builtin_trunc(px);
-                j = (uint32_t)__builtin_trunc(py);
+                i = cell_u32(px);  // (the handler uses them after `in` or slow_step vouched for them)
+                j = cell_u32(py);
                 o.dx = readlane_f64(d, 0);
                 o.dy = readlane_f64(d, 1);
                 o.sx = readlane_f64(pn, 0);
@@ -212,10 +246,9 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
             } else
             for (;;) {
                 EIK_P2PROBE(0);
-                i = (uint32_t)__builtin_trunc(px);
-                j = (uint32_t)__builtin_trunc(py);
-                in = !__builtin_isnan(px + py) && (int)i >= win.lo_x && (int)i <= win.hi_x && (int)j >= win.lo_y &&
-                     (int)j <= win.hi_y;
+                i = cell_u32(px);
+                j = cell_u32(py);
+                in = fast_cell(i, j);
                 unsigned off = (unsigned)(((int)j - win.cy0i) * kPW + ((int)i - win.cx0i)) * (unsigned)sizeof(double2);
                 off = off <= kWinBytes - (kPW + 2) * sizeof(double2) ? off : 0u;  // unsigned: negatives too
                 const double2* g = reinterpret_cast<const double2*>(reinterpret_cast<const char*>(s.g[win.cur]) + off);
@@ -265,10 +298,10 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
     } else {
         for (; k < kmax; ++k) {
             EIK_P2PROBE(0);
-            const uint32_t i = (uint32_t)__builtin_trunc(px), j = (uint32_t)__builtin_trunc(py);
-            // one test on the chain: NaN point, out of range, or window bookkeeping due
-            if (__builtin_isnan(px + py) || (int)i < win.lo_x || (int)i > win.hi_x || (int)j < win.lo_y ||
-                (int)j > win.hi_y) {
+            const uint32_t i = cell_u32(px), j = cell_u32(py);
+            // one test on the chain: a coordinate the conversion clamped, out of range, cell 0, or
+            // window bookkeeping due
+            if (!fast_cell(i, j)) {
                 if (!slow_step(i, j)) break;
             }
             EIK_P2PROBE(1);
@@ -296,7 +329,9 @@ __global__ __launch_bounds__(kPathThreads) void gdm2d_kernel(A arg) {
             if (stop) break;
         }
     }
-    if (k == kmax && kmax < a.steps && status == kGdmDone) status = kGdmError;  // out of point budget
+    // Out of point budget: the loop ended (step count, point budget or stop radius) with no row left
+    // for `end` -- n = cap, also when the stop radius was reached by the step that wrote row cap - 1.
+    if (status == kGdmDone && n >= a.cap) status = kGdmError;
     __hip_atomic_store(&s.req_seq, -1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);  // builders exit
     EIK_P2FLUSH;
     if (lead) {
@@ -531,11 +566,7 @@ __device__ __forceinline__ void wave_lds_sync() { asm volatile("s_waitcnt lgkmcn
 // (where clamping is truncation: (-1, 0) -> 0, as numpy) and decides every other coordinate itself
 // (DESIGN 3.4b); a finite coordinate's clamped rint, INT_MIN / INT_MAX, fails the same range tests
 // as the exact value.  No index is formed from a clamped or wrapped conversion.
-__device__ __forceinline__ uint32_t cvt_u32(double x) {
-    uint32_t r;
-    asm("v_cvt_u32_f64 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
+// (cvt_u32: above gdm2d_kernel)
 __device__ __forceinline__ int rint_i32(double x) {
     int r;
     asm("v_cvt_i32_f64 %0, %1" : "=v"(r) : "v"(__builtin_rint(x)));
@@ -1082,6 +1113,9 @@ __global__ __launch_bounds__(kP3Threads) void gdm3d_kernel(A arg) {
     }
     if (pending) wait_built();  // no build may still be writing when the builders are told to quit
     __hip_atomic_store(&sl.req_seq, -1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    // as the 2D walker: a loop that ended (steps or stop radius) with no row left for `end` is out
+    // of point budget
+    if (status == kGdmDone && n >= a.cap) status = kGdmError;
     if (lead) {
         if (status == kGdmDone && n < a.cap) {  // :269
             out[3 * n] = a.end[0];

@@ -28,6 +28,7 @@ EXPECT = {
     "run_cap50": (0, 401, (399, 1, 0, 0, 0, 399)),
     "run_cap257": (0, 401, (399, 1, 0, 0, 0, 399)),
     "run_cap258": (0, 401, (399, 1, 0, 0, 0, 399)),
+    "run_cap400": (0, 401, (399, 1, 0, 0, 0, 399)),
     "cone_tau05": (0, 30002, (0, 0, 0, 0, 3527, 30000)),
     "cone_tau17": (0, 8826, (0, 0, 0, 0, 1103, 8824)),
     "constant": (2, 2, (0, 0, 0, 0, 1, 1)),

@@ -79,7 +79,7 @@ def _corridor(side, tau, first, last=0, cap=None):
     return build
 
 
-STRETCH_CAPS = (2, 3, 50, 257, 258)
+STRETCH_CAPS = (2, 3, 50, 257, 258, 400)  # 400: the 401-row walk less its `end` row
 
 # ---------------------------------------------------------------- trilinear steps on a cone
 SINK = (8.3, 4.6, 4.2)
