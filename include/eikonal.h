@@ -365,10 +365,12 @@ int eik_tmap2d_update_f64(eik_ctx* ctx, const double* cost_new, double* T_inout,
  * eik_fim2d_start_seeds  asynchronous; eik_fim2d_iterate then converges it.
  * eik_fim2d_solve_seeds  start + iterate to convergence (synchronous); a full priority-band ring falls
  *                        back to the FIFO with the same seeds, as in eik_fim2d_solve.
- * The incremental re-solve knows one goal: after a seeded start, eik_fim2d_update, eik_fim2d_resolve and
- * eik_tmap2d_update_* (the context's cached solver after eik_tmap2d_seeds_*) return EIK_ERR_ARG ("the
- * bound solve has a seed set") until an eik_fim2d_start / eik_fim2d_solve / eik_fim2d_adopt (any
- * single-goal host solve on the context) binds a single-goal solve again.
+ * Replanning after a seeded solve: eik_fim2d_update_seeds / eik_fim2d_resolve_seeds below, which take
+ * cost changes and seed-list changes.  The single-goal calls stay single-goal: after a seeded start,
+ * eik_fim2d_update, eik_fim2d_resolve and eik_tmap2d_update_* (the context's cached solver after
+ * eik_tmap2d_seeds_*) return EIK_ERR_ARG ("the bound solve has a seed set") until an eik_fim2d_start /
+ * eik_fim2d_solve / eik_fim2d_adopt (any single-goal host solve on the context) binds a single-goal
+ * solve again.
  * Not covered: 3D and layered solves, the bidirectional fronts, a seeded eik_plan2d_batch. */
 int eik_fim2d_start_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
                           const int32_t* map_of, int64_t K, void* stream);
@@ -401,6 +403,75 @@ int eik_tmap2d_seeds_f32(eik_ctx* ctx, const float* cost, int64_t H, int64_t W, 
                          int64_t K, float* T, int32_t* labels);
 int eik_tmap2d_seeds_f64(eik_ctx* ctx, const double* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
                          int64_t K, double* T, int32_t* labels);
+
+/* Replanning for goal sets: the incremental re-solve of a seeded field after cost changes AND seed-list
+ * changes (no reference counterpart).  A goal dropped (sample collected, site ruled
+ * out), added, or its start value changed is the same kind of event as a cost change.
+ *
+ * The solver remembers the bound seed list as a host copy: eik_fim2d_start_seeds / eik_fim2d_solve_seeds
+ * set it, eik_fim2d_adopt_seeds sets it, every successful eik_fim2d_update_seeds replaces it.
+ *
+ * The rule.  One map.  The OLD seed list produced the converged field T_old.  The NEW list may be the
+ * same.  For a cell c, b_old(c) is the smallest (R)t0 of the old seeds on c, or +inf if there is none.
+ * b_new(c) is the same for the new list.  R is the solver's dtype and values compare as bit patterns.
+ *   Root.           c is an old root when b_old(c) is finite and T_old[c] == b_old(c) bit for bit.  This
+ *                   is the label rule's root.  A dominated seed, with T_old[c] < b_old(c), is an
+ *                   ordinary cell.
+ *   Spared root.    An old root with b_new(c) <= b_old(c).  It is never in the cone and hands no mark
+ *                   on.  Its value is a boundary condition and its own cost is not used.  The single
+ *                   goal of eik_fim2d_update is the case K = 1, t0 = 0.
+ *   Released root.  An old root with b_new(c) > b_old(c), where removal means +inf.  It is a cone seed.
+ *   Cone.           The cone is the closure of "p joins if a 4-neighbour q in the cone has
+ *                   T_old(q) <= T_old(p), p finite, p not a spared root".  It is seeded with the
+ *                   finite-T_old cells of the EIK_CHANGE_ANY rectangles and with the released roots.
+ *   Restart state.  +inf on the cone and T_old elsewhere, then T[c] = min(T[c], b_new(c)) at every new
+ *                   seed.  This state is a supersolution of the new problem.  The ordinary persistent
+ *                   solve descends from it to the fixed point of the new cost and new list, which is
+ *                   the field eik_fim2d_solve_seeds would give.
+ *   Lowering edits. Lowered rectangles, added seeds and lowered t0 need no reset.
+ *
+ * rects, kinds, K: exactly as in eik_fim2d_update (semantics, kinds, clipping, K <= 1024).  seeds, t0,
+ * Ks: the new list, checked as in eik_fim2d_start_seeds (a message names the offending index);
+ * seeds == NULL with Ks == 0: the list stays as it is.  K == 0 with an unchanged list is a no-op:
+ * nothing is queued, T keeps its bits, the info is zero and the solver stays converged.
+ *
+ * EIK_ERR_ARG with a message and nothing launched: everything eik_fim2d_update refuses (B > 1, ghost
+ * strips, a layered block, not the persistent mode, a solver never started or adopted, a last solve that
+ * did not converge, bad rectangles), a bad seed list, and a bound solve without a seed set ("the bound
+ * solve has a single goal: eik_fim2d_update, or eik_fim2d_adopt_seeds first").
+ *
+ * eik_fim2d_adopt_seeds    binds d_cost / d_T where d_T is, by the caller's word, the converged field of
+ *                          some earlier cost of this raster for this seed list; nothing is solved.
+ * eik_fim2d_update_seeds   asynchronous: invalidates, re-seeds and queues the restart; eik_fim2d_iterate
+ *                          then converges it.  The host arrays may be reused at once.
+ * eik_fim2d_resolve_seeds  update + iterate to convergence (synchronous); a full priority-band ring
+ *                          falls back to a full eik_fim2d_solve_seeds of the new list on the FIFO
+ *                          (eik_fim2d_update_info out[5] = 1).
+ * eik_fim2d_update_info    as for eik_fim2d_update: the cells invalidated include the released roots,
+ *                          the tiles queued include those the new seeds queued.
+ * Failures are those of eik_fim2d_resolve: after an error of the invalidation or of the re-solve the
+ * bound T is INVALID -- it may hold sign-marked (negative) values and a partly reset cone, and spared
+ * roots that were lifted for the invalidation may read +inf.  Solve from scratch
+ * (eik_fim2d_solve_seeds) before the field or a further update is used.
+ * Not covered: B > 1, layered and 3D solves, a seeded eik_plan2d_batch. */
+int eik_fim2d_adopt_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                          int64_t Ks, void* stream);
+int eik_fim2d_update_seeds(eik_fim2d* fim, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
+                           const double* t0, int64_t Ks, void* stream);
+int eik_fim2d_resolve_seeds(eik_fim2d* fim, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
+                            const double* t0, int64_t Ks, void* stream);
+/* Host buffers: cost_new and T, the converged field of the earlier cost for the old list, go up; T comes
+ * back as the field of cost_new for the new list (adopt_seeds with the old list, then resolve_seeds with
+ * the new one, on the context's cached solver).  seeds_new == NULL with K_new == 0: the list is
+ * unchanged.  labels != NULL: the labels of the new list, taken while the field is on the device. */
+int eik_tmap2d_update_seeds_f32(eik_ctx* ctx, const float* cost_new, float* T_inout, int64_t H, int64_t W,
+                                const int64_t* seeds_old, const double* t0_old, int64_t K_old, const int64_t* seeds_new,
+                                const double* t0_new, int64_t K_new, const int64_t* rects, const int* kinds, int64_t K,
+                                int32_t* labels);
+int eik_tmap2d_update_seeds_f64(eik_ctx* ctx, const double* cost_new, double* T_inout, int64_t H, int64_t W,
+                                const int64_t* seeds_old, const double* t0_old, int64_t K_old, const int64_t* seeds_new,
+                                const double* t0_new, int64_t K_new, const int64_t* rects, const int* kinds, int64_t K,
+                                int32_t* labels);
 
 /* Live domain decomposition (no reference counterpart: the multi-GPU split of SURVEY.md §8(e)).
  * eik_fim2d_launch(fim, 1) starts ONE persistent launch on the bound stream and returns at once.

@@ -301,6 +301,45 @@ def computeTmapMulti(costMap, goals, offsets=None, labels=False):
     return res.astype(np.float64, copy=False)
 
 
+def updateTmapMulti(costMap, Tmap, goals, changed, offsets=None, newGoals=None, newOffsets=None, labels=False):
+    """No reference counterpart: the field computeTmapMulti(costMap, newGoals, newOffsets) would return,
+    from Tmap -- the field computeTmapMulti returned for `goals` / `offsets` and an earlier costMap that
+    differs from this one only inside `changed` (rectangles or a boolean mask, as in updateTmap).
+    newGoals=None: the goal set is unchanged (newOffsets then needs newGoals).  Only the cells whose old
+    value depended on a changed cell, or on a goal that was dropped or whose offset went up, are solved
+    again.  The inputs are not modified; the result is float64, or with labels=True
+    (T, labels) with labels indexing the new goals."""
+    cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
+    if np.shape(Tmap) != cost.shape:
+        raise ValueError(f"updateTmapMulti: Tmap has shape {np.shape(Tmap)}, costMap {cost.shape}")
+    ch = np.asarray(changed)
+    if ch.dtype == bool and ch.shape != cost.shape:
+        raise ValueError(f"updateTmapMulti: the mask has shape {ch.shape}, costMap {cost.shape}")
+    g = _goal_list(goals, cost.shape)
+    if len(g) == 0:
+        raise ValueError("updateTmapMulti: no goal")
+    if offsets is not None and len(np.ravel(offsets)) != len(g):
+        raise ValueError(f"updateTmapMulti: {len(g)} goals but {len(np.ravel(offsets))} offsets")
+    gn = None
+    if newGoals is not None:
+        gn = _goal_list(newGoals, cost.shape)
+        if len(gn) == 0:
+            raise ValueError("updateTmapMulti: no new goal (None keeps the goals)")
+        if newOffsets is not None and len(np.ravel(newOffsets)) != len(gn):
+            raise ValueError(f"updateTmapMulti: {len(gn)} new goals but {len(np.ravel(newOffsets))} new offsets")
+    elif newOffsets is not None:
+        raise ValueError("updateTmapMulti: newOffsets without newGoals")
+    rects = _mask_rects(ch) if ch.dtype == bool and ch.shape == cost.shape else [tuple(int(v) for v in r) for r in changed]
+    if not rects and gn is None:
+        T = np.array(Tmap, dtype=np.float64, order="C")
+        return (T, _ctx().labels2d(np.ascontiguousarray(Tmap, dtype=_DTYPE), g, offsets)) if labels else T
+    res = _ctx().tmap2d_update_seeds(cost, np.ascontiguousarray(Tmap, dtype=_DTYPE), g, offsets, rects, seeds_new=gn,
+                                     t0_new=newOffsets, dtype=_DTYPE, labels=labels)
+    if labels:
+        return res[0].astype(np.float64, copy=False), res[1]
+    return res.astype(np.float64, copy=False)
+
+
 def getPathsToNearest(totalCostMap, labels, goals, initWaypoints, tau, safe=False):
     """No reference counterpart: from every row of initWaypoints (P, 2), getPathGDM to the goal its cell
     belongs to -- goals[labels[node(start)]], with (totalCostMap, labels) from computeTmapMulti(...,

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "seed_diff.hpp"
+
 namespace eik {
 
 // One FIM solve over B maps of H x W (or one subdomain of a decomposed raster).
@@ -145,6 +147,12 @@ struct SeedDesc {
 // after fim2d_init with no goal: T[seed] = min(T, t0) (and the edge columns' copy), the seeds' tiles and
 // the neighbours across the tile sides they lie on activated with key t0 (either mode)
 hipError_t fim2d_start_seeds(const Fim2dArgs& a, bool f64, const SeedDesc* d_seeds, int64_t K, hipStream_t st);
+// The re-solve of a seeded field (replan.hip; RootDesc: seed_diff.hpp), in stream order
+// around the kernels above: roots after prep phase 0 (a: the FIFO form, as for the flood), unlift after
+// the flood, reseed after replan_reset (a: the solve's form).  n, K >= 1.
+hipError_t replan_roots(const Fim2dArgs& a, const ReplanArgs& r, bool f64, RootDesc* d_roots, int64_t n, hipStream_t st);
+hipError_t replan_unlift(const Fim2dArgs& a, bool f64, const RootDesc* d_roots, int64_t n, hipStream_t st);
+hipError_t replan_reseed(const Fim2dArgs& a, const ReplanArgs& r, bool f64, const SeedDesc* d_seeds, int64_t K, hipStream_t st);
 constexpr int kLabelPasses = 32;  // pointer-jumping passes at most (n < 2^31 cells)
 struct LabelArgs {
     const void* T;           // [B][H][W] converged field (R), device

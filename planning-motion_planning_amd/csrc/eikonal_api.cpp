@@ -131,11 +131,13 @@ struct DescBlock {
     hipEvent_t ev = nullptr;
 };
 
-// The seeds of one multi-source call (eik_fim2d_start_seeds, eik_labels2d_dev): a pinned host block
-// and its device twin, grown on demand; ev marks the block's last upload (waited for before reuse).
-struct SeedStage {
-    SeedDesc* h = nullptr;
-    SeedDesc* d = nullptr;
+// The seeds of one multi-source call (eik_fim2d_start_seeds, eik_labels2d_dev), or the root entries of one
+// seeded update (eik_fim2d_update_seeds): a pinned host block and its device twin, grown on demand; ev
+// marks the block's last upload (waited for before reuse).
+template <typename D>
+struct Stage {
+    D* h = nullptr;
+    D* d = nullptr;
     int64_t cap = 0;
     hipEvent_t ev = nullptr;
     void release() {
@@ -147,6 +149,9 @@ struct SeedStage {
         cap = 0;
     }
 };
+
+using SeedStage = Stage<SeedDesc>;
+using RootStage = Stage<RootDesc>;
 
 }  // namespace
 
@@ -252,9 +257,12 @@ struct eik_fim2d {
     bool need_rewind = false;            // a launch without its queue rewind ran since the last init
     bool band_overflow = false;          // the last launch stopped on a full priority band (qerror bit 4)
     bool no_bands = false;               // ... so this solver's next starts use the FIFO
-    // a seed set started the bound solve (eik_fim2d_start_seeds): the re-solve knows one goal only
+    // a seed set started the bound solve (eik_fim2d_start_seeds): eik_fim2d_update knows one goal only,
+    // eik_fim2d_update_seeds re-solves it
     bool seeded = false;
     SeedStage sd;                        // its seeds
+    std::vector<SeedDesc> bound;         // the bound seed list (host copy: start_seeds, adopt_seeds, update_seeds)
+    RootStage roots;                     // eik_fim2d_update_seeds: the old list's cells (seed_diff.hpp)
     int64_t last_active = -1;            // tiles left by the last persistent launch read back (-1: none yet, or it failed)
     // incremental re-solve (replan.hip): descriptors (pinned + device), recorded tiles, counters
     DevBuf rp_rects, rp_list, rp_flag, rp_info;
@@ -389,6 +397,28 @@ static hipError_t dev_to_host(eik_ctx* c, void* dst, const void* src, size_t byt
         c->pool->copy(static_cast<char*>(dst) + off, c->stage[b], std::min(kStageChunk, bytes - off));
     }
     return hipSuccess;
+}
+
+// the checked seeds (or root entries) into the block's pinned half and on to the device in stream order
+template <typename D>
+static int seeds_upload(eik_ctx* c, Stage<D>& s, const std::vector<D>& v, hipStream_t st) {
+    const int64_t K = (int64_t)v.size();
+    if (!s.ev) HIPCHK(c, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    HIPCHK(c, hipEventSynchronize(s.ev));  // the block's last upload (a never-recorded event is complete)
+    if (s.cap < K) {
+        if (s.h) (void)hipHostFree(s.h);
+        if (s.d) (void)hipFree(s.d);
+        s.h = s.d = nullptr;
+        s.cap = 0;
+        const int64_t cap = std::max<int64_t>(1024, K);
+        HIPCHK(c, hipHostMalloc((void**)&s.h, sizeof(D) * cap));
+        HIPCHK(c, hipMalloc((void**)&s.d, sizeof(D) * cap));
+        s.cap = cap;
+    }
+    memcpy(s.h, v.data(), sizeof(D) * (size_t)K);
+    HIPCHK(c, hipMemcpyAsync(s.d, s.h, sizeof(D) * (size_t)K, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipEventRecord(s.ev, st));
+    return EIK_OK;
 }
 
 extern "C" {
@@ -628,6 +658,7 @@ void eik_fim2d_destroy(eik_fim2d* f) {
     if (f->h_rects) (void)hipHostFree(f->h_rects);
     if (f->h_info) (void)hipHostFree(f->h_info);
     f->sd.release();
+    f->roots.release();
     for (hipEvent_t ev : f->ev_rp)
         if (ev) (void)hipEventDestroy(ev);
     for (auto ev : f->ev_pool) (void)hipEventDestroy(ev);
@@ -789,27 +820,6 @@ static int seeds_check(eik_ctx* c, const char* who, int64_t B, int64_t H, int64_
     return EIK_OK;
 }
 
-// the checked seeds into the block's pinned half and on to the device in stream order
-static int seeds_upload(eik_ctx* c, SeedStage& s, const std::vector<SeedDesc>& v, hipStream_t st) {
-    const int64_t K = (int64_t)v.size();
-    if (!s.ev) HIPCHK(c, hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    HIPCHK(c, hipEventSynchronize(s.ev));  // the block's last upload (a never-recorded event is complete)
-    if (s.cap < K) {
-        if (s.h) (void)hipHostFree(s.h);
-        if (s.d) (void)hipFree(s.d);
-        s.h = s.d = nullptr;
-        s.cap = 0;
-        const int64_t cap = std::max<int64_t>(1024, K);
-        HIPCHK(c, hipHostMalloc((void**)&s.h, sizeof(SeedDesc) * cap));
-        HIPCHK(c, hipMalloc((void**)&s.d, sizeof(SeedDesc) * cap));
-        s.cap = cap;
-    }
-    memcpy(s.h, v.data(), sizeof(SeedDesc) * (size_t)K);
-    HIPCHK(c, hipMemcpyAsync(s.d, s.h, sizeof(SeedDesc) * (size_t)K, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipEventRecord(s.ev, st));
-    return EIK_OK;
-}
-
 int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
                           const int32_t* map_of, int64_t K, void* stream) {
     if (!f) return EIK_ERR_ARG;
@@ -832,6 +842,7 @@ int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int
     HIPCHK(c, fim2d_start_seeds(f->a, f->f64, f->sd.d, K, f->stream));
     f->started = true;
     f->seeded = true;
+    f->bound = std::move(v);
     f->need_rewind = false;  // the init cleared the queue words
     return EIK_OK;
 }
@@ -1202,6 +1213,34 @@ static int replan_buffers(eik_fim2d* f, ReplanArgs* r) {
     return EIK_OK;
 }
 
+// The rectangles of an update, checked and clipped (eik_fim2d_update, eik_fim2d_update_seeds): every
+// failure is EIK_ERR_ARG with the offending index.  *any: an EIK_CHANGE_ANY rectangle is among them.
+static int replan_rects_check(eik_fim2d* f, const char* who, const int64_t* rects, const int* kinds, int64_t K,
+                              std::vector<ReplanRect>& v, bool* any) {
+    eik_ctx* c = f->ctx;
+    if (K < 0 || K > kMaxRects) return set_err(c, EIK_ERR_ARG, "%s: K = %ld outside [0, %d]", who, (long)K, kMaxRects);
+    if (K > 0 && !rects) return set_err(c, EIK_ERR_ARG, "%s: rects is NULL", who);
+    v.resize((size_t)K);
+    *any = false;
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t x0 = rects[4 * k], y0 = rects[4 * k + 1], x1 = rects[4 * k + 2], y1 = rects[4 * k + 3];
+        const int kind = kinds ? kinds[k] : kChangeAny;
+        if (kind != kChangeAny && kind != kChangeLowered)
+            return set_err(c, EIK_ERR_ARG, "%s: rectangle %ld has kind %d (0 or 1)", who, (long)k, kind);
+        if (x1 <= x0 || y1 <= y0)
+            return set_err(c, EIK_ERR_ARG, "%s: rectangle %ld (%ld, %ld, %ld, %ld) is empty", who, (long)k, (long)x0, (long)y0,
+                           (long)x1, (long)y1);
+        const int64_t cx0 = std::max<int64_t>(x0, 0), cy0 = std::max<int64_t>(y0, 0);
+        const int64_t cx1 = std::min<int64_t>(x1, f->W), cy1 = std::min<int64_t>(y1, f->H);
+        if (cx1 <= cx0 || cy1 <= cy0)
+            return set_err(c, EIK_ERR_ARG, "%s: rectangle %ld (%ld, %ld, %ld, %ld) lies outside %ldx%ld", who, (long)k, (long)x0,
+                           (long)y0, (long)x1, (long)y1, (long)f->H, (long)f->W);
+        v[k] = ReplanRect{(int32_t)cx0, (int32_t)cy0, (int32_t)cx1, (int32_t)cy1, kind, 0};
+        *any |= kind == kChangeAny;
+    }
+    return EIK_OK;
+}
+
 int eik_fim2d_update(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
     if (!f) return EIK_ERR_ARG;
     eik_ctx* c = f->ctx;
@@ -1216,26 +1255,10 @@ int eik_fim2d_update(eik_fim2d* f, const int64_t* rects, const int* kinds, int64
         return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the bound solve did not run in the persistent mode");
     if (f->last_active != 0)
         return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the last solve did not end converged (0 active tiles)");
-    if (K < 0 || K > kMaxRects) return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: K = %ld outside [0, %d]", (long)K, kMaxRects);
-    if (K > 0 && !rects) return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rects is NULL");
-    std::vector<ReplanRect> v((size_t)K);
+    std::vector<ReplanRect> v;
     bool any = false;
-    for (int64_t k = 0; k < K; ++k) {
-        const int64_t x0 = rects[4 * k], y0 = rects[4 * k + 1], x1 = rects[4 * k + 2], y1 = rects[4 * k + 3];
-        const int kind = kinds ? kinds[k] : kChangeAny;
-        if (kind != kChangeAny && kind != kChangeLowered)
-            return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rectangle %ld has kind %d (0 or 1)", (long)k, kind);
-        if (x1 <= x0 || y1 <= y0)
-            return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rectangle %ld (%ld, %ld, %ld, %ld) is empty", (long)k, (long)x0,
-                           (long)y0, (long)x1, (long)y1);
-        const int64_t cx0 = std::max<int64_t>(x0, 0), cy0 = std::max<int64_t>(y0, 0);
-        const int64_t cx1 = std::min<int64_t>(x1, f->W), cy1 = std::min<int64_t>(y1, f->H);
-        if (cx1 <= cx0 || cy1 <= cy0)
-            return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: rectangle %ld (%ld, %ld, %ld, %ld) lies outside %ldx%ld", (long)k,
-                           (long)x0, (long)y0, (long)x1, (long)y1, (long)f->H, (long)f->W);
-        v[k] = ReplanRect{(int32_t)cx0, (int32_t)cy0, (int32_t)cx1, (int32_t)cy1, kind, 0};
-        any |= kind == kChangeAny;
-    }
+    rc = replan_rects_check(f, "eik_fim2d_update", rects, kinds, K, v, &any);
+    if (rc) return rc;
     ReplanArgs r{};
     rc = replan_buffers(f, &r);
     // options, budgets and the priority bands (their width from the NEW cost) as eik_fim2d_start sets them
@@ -1314,6 +1337,141 @@ int eik_fim2d_adopt(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     f->seeded = false;
     f->need_rewind = false;
     f->last_active = 0;
+    return EIK_OK;
+}
+
+// ---- the re-solve of a seeded field: cost and seed-list changes (replan.hip)
+int eik_fim2d_adopt_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0, int64_t Ks,
+                          void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    const char* who = "eik_fim2d_adopt_seeds";
+    if (!d_cost || !d_T) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_cost ? "d_cost" : "d_T");
+    int rc = replan_gate(f, who);
+    if (rc) return rc;
+    std::vector<SeedDesc> v;
+    rc = seeds_check(c, who, 1, f->H, f->W, f->f64, seeds, t0, nullptr, Ks, v);
+    if (rc) return rc;
+    ReplanArgs r{};
+    rc = replan_buffers(f, &r);
+    if (!rc) rc = fim2d_configure(f, d_cost, d_T, stream);
+    const int64_t none[2] = {-1, -1};  // no goal, as after eik_fim2d_start_seeds
+    if (!rc) rc = upload_goals(f, none);
+    if (rc) return rc;
+    HIPCHK(c, replan_adopt(f->a, f->f64, f->stream));
+    HIPCHK(c, replan_prep(f->a, r, 0, f->stream));  // the queue as after a converged solve
+    HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    f->rp_timed = false;
+    f->rp_fallback = false;
+    f->started = true;
+    f->seeded = true;
+    f->bound = std::move(v);
+    f->need_rewind = false;
+    f->last_active = 0;
+    return EIK_OK;
+}
+
+int eik_fim2d_update_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
+                           const double* t0, int64_t Ks, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    const char* who = "eik_fim2d_update_seeds";
+    int rc = replan_gate(f, who);
+    if (rc) return rc;
+    if (!f->started || !f->a.cost || !f->a.T) return set_err(c, EIK_ERR_ARG, "%s: the solver was never started or adopted", who);
+    if (!f->seeded || f->bound.empty())
+        return set_err(c, EIK_ERR_ARG, "%s: the bound solve has a single goal: eik_fim2d_update, or eik_fim2d_adopt_seeds first", who);
+    if (f->a.mode != kModePersistent) return set_err(c, EIK_ERR_ARG, "%s: the bound solve did not run in the persistent mode", who);
+    if (f->last_active != 0) return set_err(c, EIK_ERR_ARG, "%s: the last solve did not end converged (0 active tiles)", who);
+    std::vector<ReplanRect> v;
+    bool any = false;
+    rc = replan_rects_check(f, who, rects, kinds, K, v, &any);
+    if (rc) return rc;
+    // the new list (seeds == NULL with Ks == 0: the bound one stays) and its diff against the bound one
+    std::vector<SeedDesc> nw;
+    if (!seeds && Ks == 0)
+        nw = f->bound;
+    else
+        rc = seeds_check(c, who, 1, f->H, f->W, f->f64, seeds, t0, nullptr, Ks, nw);
+    if (rc) return rc;
+    std::vector<SeedCell> co(f->bound.size()), cn(nw.size());
+    for (size_t k = 0; k < co.size(); ++k) co[k] = SeedCell{f->bound[k].x, f->bound[k].y, f->bound[k].t0};
+    for (size_t k = 0; k < cn.size(); ++k) cn[k] = SeedCell{nw[k].x, nw[k].y, nw[k].t0};
+    std::vector<RootDesc> roots;
+    const SeedDiff diff = seed_diff(co.data(), (int64_t)co.size(), cn.data(), (int64_t)cn.size(), roots);
+    const bool flood = any || diff.released > 0;  // there is a cone to find: the roots take part
+    ReplanArgs r{};
+    rc = replan_buffers(f, &r);
+    // options, budgets and the priority bands (their width from the NEW cost) as eik_fim2d_start sets them
+    if (!rc) rc = fim2d_configure(f, f->a.cost, f->a.T, stream);
+    if (rc) return rc;
+    r.K = (int)K;
+    if (K > 0) {
+        memcpy(f->h_rects, v.data(), sizeof(ReplanRect) * (size_t)K);
+        HIPCHK(c, hipMemcpyAsync(f->rp_rects.p, f->h_rects, sizeof(ReplanRect) * (size_t)K, hipMemcpyHostToDevice, f->stream));
+    }
+    if (flood) rc = seeds_upload(c, f->roots, roots, f->stream);
+    if (!rc) rc = seeds_upload(c, f->sd, nw, f->stream);
+    if (rc) return rc;
+    // the flood runs on the plain FIFO of the solver's queue
+    Fim2dArgs fa = f->a;
+    fa.bctl = nullptr;
+    fa.fresh_first = 0;
+    fa.qhold = nullptr;
+    fa.live = nullptr;
+    fa.edge_dirty = nullptr;
+    const int64_t nroots = (int64_t)roots.size();
+    HIPCHK(c, hipEventRecord(f->ev_rp[0], f->stream));
+    HIPCHK(c, replan_prep(fa, r, 0, f->stream));
+    if (flood) {
+        if (f->flood_grid == 0) f->flood_grid = replan_flood_resident(f->f64, c->cu_count);
+        const int g = std::max(1, std::min(c->grid > 0 ? c->grid : 4 * c->cu_count, f->flood_grid));
+        HIPCHK(c, replan_roots(fa, r, f->f64, f->roots.d, nroots, f->stream));
+        HIPCHK(c, replan_seed(fa, r, f->f64, f->stream));
+        HIPCHK(c, replan_flood(fa, r, f->f64, g, f->stream));
+        HIPCHK(c, replan_unlift(fa, f->f64, f->roots.d, nroots, f->stream));
+    }
+    HIPCHK(c, replan_prep(f->a, r, 1, f->stream));
+    if (K > 0 || diff.released > 0) HIPCHK(c, replan_reset(f->a, r, f->f64, f->stream));
+    // (always: a dominated seed of an unchanged list may lie in the cone, and is put back at its t0)
+    HIPCHK(c, replan_reseed(f->a, r, f->f64, f->sd.d, (int64_t)nw.size(), f->stream));
+    HIPCHK(c, hipEventRecord(f->ev_rp[1], f->stream));
+    HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+    f->rp_timed = true;
+    f->rp_fallback = false;
+    f->need_rewind = false;  // the prep cleared the queue words
+    f->bound = std::move(nw);
+    if (K == 0 && diff.same) f->last_active = 0;  // nothing queued: still converged
+    return EIK_OK;
+}
+
+int eik_fim2d_resolve_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
+                            const double* t0, int64_t Ks, void* stream) {
+    int rc = eik_fim2d_update_seeds(f, rects, kinds, K, seeds, t0, Ks, stream);
+    if (rc) return rc;
+    int64_t active = 0;
+    f->defer_sync = true;
+    rc = eik_fim2d_iterate(f, f->max_iters, &active);
+    f->defer_sync = false;
+    if (!rc) rc = finish_solve(f, &active);
+    if (rc && f->band_overflow) {  // a priority band's ring was full: a full seeded solve on the FIFO, the new list
+        f->band_overflow = false;
+        f->no_bands = true;
+        const std::vector<SeedDesc> b = f->bound;
+        std::vector<int64_t> s(2 * b.size());
+        std::vector<double> t(b.size());
+        for (size_t k = 0; k < b.size(); ++k) {
+            s[2 * k] = b[k].x;
+            s[2 * k + 1] = b[k].y;
+            t[k] = b[k].t0;
+        }
+        rc = eik_fim2d_solve_seeds(f, f->a.cost, f->a.T, s.data(), t.data(), nullptr, (int64_t)b.size(), stream);
+        f->rp_fallback = true;
+        return rc;
+    }
+    if (rc) return rc;
+    if (active != 0)
+        return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence of the re-solve (%ld tiles left; negative costs?)", (long)active);
     return EIK_OK;
 }
 
@@ -1745,7 +1903,62 @@ static int tmap_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, cons
     return EIK_OK;
 }
 
+// cost_new and the converged field of the earlier cost and the old list go up; adopt_seeds + resolve_seeds
+// on the cached solver; labels (optional) of the new list from the field while it is on the device
+template <typename R>
+static int tmap_update_seeds_host(eik_ctx* c, const R* cost, R* T, int64_t H, int64_t W, const int64_t* seeds_old,
+                                  const double* t0_old, int64_t K_old, const int64_t* seeds_new, const double* t0_new,
+                                  int64_t K_new, const int64_t* rects, const int* kinds, int64_t K, int32_t* labels) {
+    if (!c) return EIK_ERR_ARG;
+    const char* who = "eik_tmap2d_update_seeds";
+    if (!cost || !T) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !cost ? "cost_new" : "T_inout");
+    if (H < 1 || W < 1) return set_err(c, EIK_ERR_ARG, "%s: bad shape %ld x %ld", who, (long)H, (long)W);
+    constexpr int dtype = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
+    std::vector<SeedDesc> v;  // (checked before anything is uploaded; the entry points below check again)
+    int rc = seeds_check(c, who, 1, H, W, sizeof(R) == 8, seeds_old, t0_old, nullptr, K_old, v);
+    const bool keep = !seeds_new && K_new == 0;  // the list is unchanged
+    if (!rc && !keep) rc = seeds_check(c, who, 1, H, W, sizeof(R) == 8, seeds_new, t0_new, nullptr, K_new, v);
+    if (rc) return rc;
+    if (labels && H * W >= (1ll << 31)) return set_err(c, EIK_ERR_ARG, "%s: labels need fewer than 2^31 cells", who);
+    const int64_t n = H * W;
+    HIPCHK(c, hipSetDevice(c->device));
+    eik_fim2d* f = nullptr;
+    rc = get_solver(c, 1, H, W, dtype, &f);
+    if (!rc) rc = replan_gate(f, who);
+    if (rc) return rc;
+    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
+    HIPCHK(c, c->T.ensure(sizeof(R) * n));
+    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
+    HIPCHK(c, host_to_dev(c, c->T.p, T, sizeof(R) * n, c->stream));
+    rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = eik_fim2d_adopt_seeds(f, c->cost.p, c->T.p, seeds_old, t0_old, K_old, c->stream);
+    if (!rc) rc = eik_fim2d_resolve_seeds(f, rects, kinds, K, seeds_new, t0_new, K_new, c->stream);
+    if (!rc && labels)
+        rc = eik_labels2d_dev(c, c->T.p, dtype, 1, H, W, keep ? seeds_old : seeds_new, keep ? t0_old : t0_new, nullptr,
+                              keep ? K_old : K_new, (int32_t*)c->lab_out.p, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
+    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
 extern "C" {
+
+int eik_tmap2d_update_seeds_f32(eik_ctx* c, const float* cost_new, float* T, int64_t H, int64_t W, const int64_t* seeds_old,
+                                const double* t0_old, int64_t K_old, const int64_t* seeds_new, const double* t0_new,
+                                int64_t K_new, const int64_t* rects, const int* kinds, int64_t K, int32_t* labels) {
+    return tmap_update_seeds_host<float>(c, cost_new, T, H, W, seeds_old, t0_old, K_old, seeds_new, t0_new, K_new, rects, kinds,
+                                         K, labels);
+}
+
+int eik_tmap2d_update_seeds_f64(eik_ctx* c, const double* cost_new, double* T, int64_t H, int64_t W, const int64_t* seeds_old,
+                                const double* t0_old, int64_t K_old, const int64_t* seeds_new, const double* t0_new,
+                                int64_t K_new, const int64_t* rects, const int* kinds, int64_t K, int32_t* labels) {
+    return tmap_update_seeds_host<double>(c, cost_new, T, H, W, seeds_old, t0_old, K_old, seeds_new, t0_new, K_new, rects, kinds,
+                                          K, labels);
+}
 
 int eik_tmap2d_seeds_f32(eik_ctx* c, const float* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
                          int64_t K, float* T, int32_t* labels) {

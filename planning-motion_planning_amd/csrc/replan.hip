@@ -442,6 +442,83 @@ __global__ __launch_bounds__(kThreads) void replan_adopt_kernel(Fim2dArgs a) {
     }
 }
 
+// ------------------------------------------------------------- seed sets
+// The re-solve of a field that a seed LIST produced (eik_fim2d_update_seeds), for a list that may have
+// changed with the cost.  Roots take the goal's place.  The host's diff (seed_diff.cpp) names every
+// distinct cell of the old list with b_old, the smallest (R)t0 of the old seeds on it, and its class:
+// keep (b_new <= b_old) or release.  With r.gx = r.gy = -1 the goal tests above never fire, and three
+// plain grid kernels around them, ordered by the stream, make the kernels above see what they need:
+//
+//   roots    before the seed kernel.  An entry whose cell does not hold b_old bit for bit is a dominated
+//            seed, an ordinary cell: nothing.  A kept ROOT is lifted to +inf -- to the seed kernel and
+//            the flood a cell that is not there, never marked and handing no mark on, as the staged goal
+//            is -- and the entry is flagged.  A released root is a cone seed like a finite cell of an ANY
+//            rectangle: sign bit, its tile recorded, the tiles of the cell dilated by one queued.
+//   unlift   after the flood, before the reset: flagged entries get b_old back, so that the reset and
+//            the rectangles kernel find the spared roots as finite kept cells, key their pushes by them
+//            and rewrite the edge columns with the roots in them.
+//   reseed   after the rectangles kernel, one thread per seed of the NEW list: T = min(T, b_new) on the
+//            bit pattern (and the edge column's copy); only a seed that lowered its cell queues its tile
+//            and the neighbours across the sides it lies on, as fim2d_seeds_kernel does.
+template <typename R>
+__global__ __launch_bounds__(256) void replan_roots_kernel(Fim2dArgs a, ReplanArgs r, RootDesc* __restrict__ roots, int n) {
+    using B = Bits<R>;
+    using U = typename B::U;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const RootDesc d = roots[k];
+    // (the host checked: 0 <= x < W, 0 <= y < H; one entry per cell, so no two threads share one)
+    U* const p = static_cast<U*>(a.T) + ((int64_t)d.y * a.W + d.x);
+    const U v = *p;
+    if (v != B::of((R)d.b_old)) return;  // undercut by another seed's wave: not a root
+    if (d.cls == kRootKeep) {
+        *p = B::inf;
+        roots[k].lifted = 1u;
+        return;
+    }
+    *p = v | B::sign;
+    const int ty = d.y / kTile, tx = d.x / kTile, ry = d.y % kTile, cx = d.x % kTile;
+    const int tile = ty * a.ntx + tx;
+    record_tile(r, tile);
+    qpush(a, tile, kSelf);
+    // a root on a tile's edge lies on its neighbour's ring
+    if (ry == 0 && ty > 0) qpush(a, tile - a.ntx, kSelf);
+    if (ry == kTile - 1 && ty + 1 < a.nty) qpush(a, tile + a.ntx, kSelf);
+    if (cx == 0 && tx > 0) qpush(a, tile - 1, kSelf);
+    if (cx == kTile - 1 && tx + 1 < a.ntx) qpush(a, tile + 1, kSelf);
+}
+
+template <typename R>
+__global__ __launch_bounds__(256) void replan_unlift_kernel(Fim2dArgs a, const RootDesc* __restrict__ roots, int n) {
+    using B = Bits<R>;
+    using U = typename B::U;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const RootDesc d = roots[k];
+    if (d.lifted) static_cast<U*>(a.T)[(int64_t)d.y * a.W + d.x] = B::of((R)d.b_old);
+}
+
+template <typename R>
+__global__ __launch_bounds__(256) void replan_reseed_kernel(Fim2dArgs a, ReplanArgs r, const SeedDesc* __restrict__ seeds, int K) {
+    using B = Bits<R>;
+    using U = typename B::U;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const SeedDesc s = seeds[k];
+    // (the host checked: inside the raster, t0 finite, >= 0 and rounded to R; one map, persistent mode)
+    const R t0 = (R)s.t0;
+    const U bits = B::of(t0);
+    const int cx = s.x % kTile, ry = s.y % kTile;
+    const int tile = (s.y / kTile) * a.ntx + s.x / kTile;
+    const U old = atomicMin(static_cast<U*>(a.T) + ((int64_t)s.y * a.W + s.x), bits);
+    if (a.ecol && (cx == 0 || cx == kTile - 1))
+        atomicMin(static_cast<U*>(a.ecol) + (((int64_t)tile * 2 + (cx == 0 ? 0 : 1)) * kTile + ry), bits);
+    if (!(old > bits)) return;  // lowered nothing: queues nothing
+    const float key = (float)t0;
+    push_counted(a, r, tile, kSelf | kVisited, key);
+    activate_seed_sides(a, tile, ry, cx, kTile, key);
+}
+
 // ------------------------------------------------------------------------- host launchers
 hipError_t replan_prep(const Fim2dArgs& a, const ReplanArgs& r, int phase, hipStream_t st) {
     static_assert(kQueueCtlBytes / 4 <= 256, "block 0 clears the queue words");
@@ -451,6 +528,7 @@ hipError_t replan_prep(const Fim2dArgs& a, const ReplanArgs& r, int phase, hipSt
 }
 
 hipError_t replan_seed(const Fim2dArgs& a, const ReplanArgs& r, bool f64, hipStream_t st) {
+    if (r.K < 1) return hipSuccess;  // (a seeded update with released roots and no rectangle)
     if (f64)
         hipLaunchKernelGGL(replan_seed_kernel<double>, dim3(r.K, 32), dim3(256), 0, st, a, r);
     else
@@ -478,10 +556,10 @@ hipError_t replan_reset(const Fim2dArgs& a, const ReplanArgs& r, bool f64, hipSt
     const int grid = (int)std::min<int64_t>(1024, a.capacity);
     if (f64) {
         hipLaunchKernelGGL(replan_reset_kernel<double>, dim3(grid), dim3(kThreads), 0, st, a, r);
-        hipLaunchKernelGGL(replan_rects_kernel<double>, dim3(r.K, 16), dim3(kThreads), 0, st, a, r);
+        if (r.K > 0) hipLaunchKernelGGL(replan_rects_kernel<double>, dim3(r.K, 16), dim3(kThreads), 0, st, a, r);
     } else {
         hipLaunchKernelGGL(replan_reset_kernel<float>, dim3(grid), dim3(kThreads), 0, st, a, r);
-        hipLaunchKernelGGL(replan_rects_kernel<float>, dim3(r.K, 16), dim3(kThreads), 0, st, a, r);
+        if (r.K > 0) hipLaunchKernelGGL(replan_rects_kernel<float>, dim3(r.K, 16), dim3(kThreads), 0, st, a, r);
     }
     return hipGetLastError();
 }
@@ -492,6 +570,33 @@ hipError_t replan_adopt(const Fim2dArgs& a, bool f64, hipStream_t st) {
         hipLaunchKernelGGL(replan_adopt_kernel<double>, dim3(grid), dim3(kThreads), 0, st, a);
     else
         hipLaunchKernelGGL(replan_adopt_kernel<float>, dim3(grid), dim3(kThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t replan_roots(const Fim2dArgs& a, const ReplanArgs& r, bool f64, RootDesc* d_roots, int64_t n, hipStream_t st) {
+    const int grid = (int)((n + 255) / 256);
+    if (f64)
+        hipLaunchKernelGGL(replan_roots_kernel<double>, dim3(grid), dim3(256), 0, st, a, r, d_roots, (int)n);
+    else
+        hipLaunchKernelGGL(replan_roots_kernel<float>, dim3(grid), dim3(256), 0, st, a, r, d_roots, (int)n);
+    return hipGetLastError();
+}
+
+hipError_t replan_unlift(const Fim2dArgs& a, bool f64, const RootDesc* d_roots, int64_t n, hipStream_t st) {
+    const int grid = (int)((n + 255) / 256);
+    if (f64)
+        hipLaunchKernelGGL(replan_unlift_kernel<double>, dim3(grid), dim3(256), 0, st, a, d_roots, (int)n);
+    else
+        hipLaunchKernelGGL(replan_unlift_kernel<float>, dim3(grid), dim3(256), 0, st, a, d_roots, (int)n);
+    return hipGetLastError();
+}
+
+hipError_t replan_reseed(const Fim2dArgs& a, const ReplanArgs& r, bool f64, const SeedDesc* d_seeds, int64_t K, hipStream_t st) {
+    const int grid = (int)((K + 255) / 256);
+    if (f64)
+        hipLaunchKernelGGL(replan_reseed_kernel<double>, dim3(grid), dim3(256), 0, st, a, r, d_seeds, (int)K);
+    else
+        hipLaunchKernelGGL(replan_reseed_kernel<float>, dim3(grid), dim3(256), 0, st, a, r, d_seeds, (int)K);
     return hipGetLastError();
 }
 

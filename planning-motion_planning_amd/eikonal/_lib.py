@@ -226,6 +226,12 @@ def lib():
         L.eik_labels2d_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, _i64p, vp, vp, i64, vp, vp]
         L.eik_tmap2d_seeds_f32.argtypes = [vp, _f32p, i64, i64, _i64p, vp, i64, _f32p, vp]
         L.eik_tmap2d_seeds_f64.argtypes = [vp, _f64p, i64, i64, _i64p, vp, i64, _f64p, vp]
+        # the re-solve of a seeded field: rects / kinds / seeds / t0 / labels are nullable host arrays
+        L.eik_fim2d_adopt_seeds.argtypes = [vp, vp, vp, _i64p, vp, i64, vp]
+        L.eik_fim2d_update_seeds.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp]
+        L.eik_fim2d_resolve_seeds.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp]
+        L.eik_tmap2d_update_seeds_f32.argtypes = [vp, _f32p, _f32p, i64, i64, _i64p, vp, i64, vp, vp, i64, vp, vp, i64, vp]
+        L.eik_tmap2d_update_seeds_f64.argtypes = [vp, _f64p, _f64p, i64, i64, _i64p, vp, i64, vp, vp, i64, vp, vp, i64, vp]
         _lib = L
         return L
 
@@ -287,6 +293,8 @@ EXPORTED = [
     "eik_tmap2d_update_f32", "eik_tmap2d_update_f64",
     "eik_fim2d_start_seeds", "eik_fim2d_solve_seeds", "eik_labels2d_dev", "eik_tmap2d_seeds_f32",
     "eik_tmap2d_seeds_f64",
+    "eik_fim2d_adopt_seeds", "eik_fim2d_update_seeds", "eik_fim2d_resolve_seeds", "eik_tmap2d_update_seeds_f32",
+    "eik_tmap2d_update_seeds_f64",
 ]
 
 
@@ -425,6 +433,34 @@ class Context:
         fn = lib().eik_tmap2d_seeds_f64 if cost.dtype == np.float64 else lib().eik_tmap2d_seeds_f32
         self._chk(fn(self._h, cost, H, W, s, _addr(t), K, T, _addr(lab)))
         return (T, lab) if labels else T
+
+    def tmap2d_update_seeds(self, cost_new, T, seeds_old, t0_old, rects, kinds=None, seeds_new=None, t0_new=None,
+                            dtype=np.float64, labels=False):
+        """The field of `cost_new` and the seed list `seeds_new` / `t0_new` (None: the old list) from T, the
+        converged field of an earlier cost for `seeds_old` / `t0_old`; the costs differ only inside `rects`
+        (as in tmap2d_update).  Only what depended on the raised cells and on the dropped or raised seeds
+        is solved again (eik_tmap2d_update_seeds_*).  The inputs are not modified.  -> T, or (T, labels of
+        the new list) with labels=True."""
+        cost = np.ascontiguousarray(cost_new, dtype=dtype)
+        H, W = cost.shape
+        if np.shape(T) != cost.shape:
+            raise ValueError(f"tmap2d_update_seeds: T has shape {np.shape(T)}, cost {cost.shape}")
+        if seeds_new is None and t0_new is not None:
+            raise ValueError("tmap2d_update_seeds: t0_new without seeds_new")
+        so, to, _, Ko = _seeds(seeds_old, t0_old)
+        sn, tn, Kn = None, None, 0
+        if seeds_new is not None:
+            sn, tn, _, Kn = _seeds(seeds_new, t0_new)
+            if Kn == 0:
+                raise ValueError("tmap2d_update_seeds: seeds_new is empty (None keeps the list)")
+        out = result_empty(cost.shape, cost.dtype)
+        out[...] = T
+        lab = np.empty(cost.shape, np.int32) if labels else None
+        r, k, K = _rects(rects, kinds)
+        fn = lib().eik_tmap2d_update_seeds_f64 if cost.dtype == np.float64 else lib().eik_tmap2d_update_seeds_f32
+        self._chk(fn(self._h, cost, out, H, W, so, _addr(to), Ko, _addr(sn), _addr(tn), Kn, r.ctypes.data if K else None,
+                     k.ctypes.data if k is not None and K else None, K, _addr(lab)))
+        return (out, lab) if labels else out
 
     def labels2d(self, T, seeds, t0=None, map_of=None):
         """Nearest-seed labels (eik_labels2d_dev) of a converged field T -- H x W or a stack B x H x W,
@@ -828,6 +864,31 @@ class Fim2d:
     def adopt(self, d_cost, d_T, goals, stream=None):
         self.ctx._chk(lib().eik_fim2d_adopt(self._h, d_cost, d_T, np.ascontiguousarray(goals, np.int64).reshape(-1),
                                             stream))
+
+    # ... of a seeded field, after cost and seed-list changes (eik_fim2d_adopt_seeds / update_seeds /
+    # resolve_seeds): seeds None keeps the bound list
+    def adopt_seeds(self, d_cost, d_T, seeds, t0=None, stream=None):
+        s, t, _, K = _seeds(seeds, t0)
+        self.ctx._chk(lib().eik_fim2d_adopt_seeds(self._h, d_cost, d_T, s, _addr(t), K, stream))
+
+    def _update_seeds(self, fn, rects, kinds, seeds, t0, stream):
+        r, k, K = _rects(rects, kinds)
+        s, t, Ks = None, None, 0
+        if seeds is not None:
+            s, t, _, Ks = _seeds(seeds, t0)
+        elif t0 is not None:
+            raise ValueError("t0 without seeds")
+        # (an empty list that is not None goes down as a pointer with Ks = 0: the library refuses it)
+        self.ctx._chk(fn(self._h, r.ctypes.data if K else None, k.ctypes.data if k is not None and K else None, K,
+                         _addr(s), _addr(t), Ks, stream))
+
+    def update_seeds(self, rects, kinds=None, seeds=None, t0=None, stream=None):
+        """asynchronous: invalidate what depended on the changed rectangles and on the released roots, put the
+        new seeds in and queue the restart; iterate() converges it"""
+        self._update_seeds(lib().eik_fim2d_update_seeds, rects, kinds, seeds, t0, stream)
+
+    def resolve_seeds(self, rects, kinds=None, seeds=None, t0=None, stream=None):
+        self._update_seeds(lib().eik_fim2d_resolve_seeds, rects, kinds, seeds, t0, stream)
 
     def update_info(self):
         o = np.zeros(6, np.int64)
