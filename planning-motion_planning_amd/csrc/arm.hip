@@ -33,6 +33,8 @@ __device__ __forceinline__ double tdot(const double* t, double x, double y, doub
     return __fma_rn(t[3], 1.0, __fma_rn(t[2], z, __fma_rn(t[1], y, __dmul_rn(t[0], x))));
 }
 
+constexpr double kTwo63 = 9223372036854775808.0;  // |x| < 2^63: the cast to long long is defined
+
 struct Ev {
     long long cell;  // -1: no write
     bool close;
@@ -81,10 +83,18 @@ __device__ __forceinline__ Ev arm_event(const ArmArgs& a, unsigned long long s) 
         if (!close) v = a.valC[kk];
     }
     Ev e{-1, close, v};
-    if (!want) return e;
-    const long long ix = (long long)rint(__ddiv_rn(tdot(T, X, Y, Z), a.resX));
-    const long long iy = (long long)rint(__ddiv_rn(tdot(T + 4, X, Y, Z), a.resY));
-    const long long iz = (long long)rint(__ddiv_rn(tdot(T + 8, X, Y, Z), a.resZ));
+    const double qx = rint(__ddiv_rn(tdot(T, X, Y, Z), a.resX));
+    const double qy = rint(__ddiv_rn(tdot(T + 4, X, Y, Z), a.resY));
+    const double qz = rint(__ddiv_rn(tdot(T + 8, X, Y, Z), a.resZ));
+    // int(round(.)) is a Python int: NaN / inf raise (*bad), any finite value converts and one
+    // beyond int64 is simply outside the volume.  Decided here, before the cast could be undefined.
+    if (!(fabs(qx) < kTwo63 && fabs(qy) < kTwo63 && fabs(qz) < kTwo63)) {
+        if (!(fabs(qx) < __builtin_inf() && fabs(qy) < __builtin_inf() && fabs(qz) < __builtin_inf()))
+            atomicOr(a.bad, 1u);
+        return e;
+    }
+    if (!want) return e;  // the reference converts these nodes too (:591-593, :631-633), then does nothing
+    const long long ix = (long long)qx, iy = (long long)qy, iz = (long long)qz;
     if (ix < 0 || iy < 0 || iz < 0 || ix >= a.sX || iy >= a.sY || iz >= a.sZ) return e;
     if (close && ((ix == a.fw[0] && iy == a.fw[1] && iz == a.fw[2]) || (ix == a.iw[0] && iy == a.iw[1] && iz == a.iw[2])))
         return e;  // never the sample / start node
@@ -137,7 +147,8 @@ __global__ void arm_obst_fill(double* fmap, double* omap, double* gmap, long lon
 }
 
 // one thread per DEM column (j, i): the surface cell becomes +inf in obstMap or groundMap and so
-// in finalMap (:327-345).  A negative z index wraps as numpy's does; *bad flags one that cannot.
+// in finalMap (:327-345).  A negative z index wraps as numpy's does; *bad bit 0 flags one that cannot,
+// bit 1 a height that is NaN or infinite.
 __global__ void arm_obst_columns(const double* Zs, const double* obst, long long m, long long n, double resX,
                                  double resY, double resZ, long long sX, long long sY, long long sZ, double xm,
                                  double ym, double* fmap, double* omap, double* gmap, unsigned* bad) {
@@ -145,13 +156,20 @@ __global__ void arm_obst_columns(const double* Zs, const double* obst, long long
     if (t >= m * n) return;
     const long long j = t / n, i = t % n;  // j: DEM row (y), i: column (x)
     if (__dmul_rn(resX, (double)i) == xm || __dmul_rn(resY, (double)j) == ym) return;
-    long long iz = (long long)rint(__ddiv_rn(Zs[t], resZ));
-    if (!(i < sX && j < sY && iz < sZ)) return;
-    if (iz < 0) iz += sZ;
-    if (iz < 0) {
+    // int(round(.)) (:334) comes before the bounds test (:335): NaN / inf raise wherever the column
+    // lies (*bad bit 1); a finite index beyond int64 is skipped above sZ and cannot wrap below -sZ
+    const double q = rint(__ddiv_rn(Zs[t], resZ));
+    if (!(fabs(q) < __builtin_inf())) {
+        atomicOr(bad, 2u);
+        return;
+    }
+    if (!(i < sX && j < sY && q < (double)sZ)) return;
+    if (q < -(double)sZ) {
         atomicOr(bad, 1u);
         return;
     }
+    long long iz = (long long)q;  // in [-sZ, sZ)
+    if (iz < 0) iz += sZ;
     const long long c = (j * sY + i) * sZ + iz;
     if (obst[t] == 1.0) {
         if (omap) omap[c] = __builtin_inf();

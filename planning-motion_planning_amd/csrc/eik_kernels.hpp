@@ -332,6 +332,7 @@ struct ArmArgs {
     double* tunnel;             // [cells] TunnelCost's Cmap
     const double* fmap;         // [cells] GetObstMap's finalMap (for out)
     double* out;                // nullable: fmap * tunnel
+    unsigned* bad;              // set when an event's node is NaN / inf (the reference raises)
 };
 hipError_t arm_obst_map(const double* Zs, const double* obst, int64_t m, int64_t n, double resX, double resY,
                         double resZ, int64_t sX, int64_t sY, int64_t sZ, double xm, double ym, double* fmap,

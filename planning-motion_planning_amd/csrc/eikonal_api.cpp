@@ -3501,6 +3501,12 @@ void arm_tables(const double* gamma2D, const double* heading, int64_t npts, cons
 
 }  // namespace
 
+// arm_obst_columns' flag: bit 1 a NaN / inf height (:334 raises), bit 0 an index below -sZ (:341 / :346)
+static int arm_obst_bad(eik_ctx* c, unsigned bad) {
+    if (bad & 2u) return set_err(c, EIK_ERR_ARG, "GetObstMap: a height is NaN or infinite (the reference raises)");
+    return set_err(c, EIK_ERR_ARG, "GetObstMap: a surface index below -sZ (the reference raises IndexError)");
+}
+
 // Build the volume on the device into d_cost (fmap * tunnel) and/or return the pieces.  d_fmap:
 // GetObstMap's finalMap (computed here when d_Z != nullptr); d_tunnel: TunnelCost's map.
 static int arm_volume_dev(eik_ctx* c, const double* d_Z, const double* d_obst, int64_t m, int64_t n,
@@ -3508,9 +3514,16 @@ static int arm_volume_dev(eik_ctx* c, const double* d_Z, const double* d_obst, i
                           double* d_fmap, double* d_omap, double* d_gmap, double* d_tunnel, double* d_cost,
                           hipStream_t st) {
     const int64_t nc = v->sX * v->sY * v->sZ;
+    // int(round(.)) of a NaN / inf raises in the reference (:558-560 and their repeats), and so does
+    // math.cos of an inf (:531-536).  Every event converts its node, so one such input fails the call;
+    // nothing is launched for it.  (A finite input whose node overflows to inf is left to the kernel.)
+    for (int64_t k = 0; k < 3 * npts; ++k)
+        if (!std::isfinite(gamma2D[k]) || !std::isfinite(heading[k]))
+            return set_err(c, EIK_ERR_ARG, "TunnelCost: base point or heading %ld is NaN or infinite (the reference raises)",
+                           (long)(k / 3));
+    HIPCHK(c, c->misc.ensure(64));
+    HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 2 * sizeof(unsigned), st));  // [0] GetObstMap, [1] TunnelCost
     if (d_Z) {
-        HIPCHK(c, c->misc.ensure(64));
-        HIPCHK(c, hipMemsetAsync(c->misc.p, 0, sizeof(unsigned), st));
         HIPCHK(c, arm_obst_map(d_Z, d_obst, m, n, v->resX, v->resY, v->resZ, v->sX, v->sY, v->sZ, v->xm, v->ym, d_fmap,
                                d_omap, d_gmap, (unsigned*)c->misc.p, st));
     }
@@ -3562,14 +3575,14 @@ static int arm_volume_dev(eik_ctx* c, const double* d_Z, const double* d_obst, i
     a.tunnel = d_tunnel;
     a.fmap = d_fmap;
     a.out = d_cost;
+    a.bad = (unsigned*)c->misc.p + 1;
     HIPCHK(c, arm_tunnel(a, st));
     // the tables must outlive the kernels: T.buf is host memory copied above; wait before return
     HIPCHK(c, hipStreamSynchronize(st));
-    if (d_Z) {
-        unsigned bad = 0;
-        HIPCHK(c, hipMemcpy(&bad, c->misc.p, sizeof bad, hipMemcpyDeviceToHost));
-        if (bad) return set_err(c, EIK_ERR_ARG, "GetObstMap: a surface index below -sZ (the reference raises IndexError)");
-    }
+    unsigned bad[2] = {0, 0};
+    HIPCHK(c, hipMemcpy(bad, c->misc.p, sizeof bad, hipMemcpyDeviceToHost));
+    if (bad[0]) return arm_obst_bad(c, bad[0]);
+    if (bad[1]) return set_err(c, EIK_ERR_ARG, "TunnelCost: a node index is infinite (the reference raises OverflowError)");
     return EIK_OK;
 }
 
@@ -3607,7 +3620,7 @@ int eik_arm_obst_map_f64(eik_ctx* c, const double* Z, const double* obst, int64_
     if (omap) HIPCHK(c, dev_to_host(c, omap, dOm, sizeof(double) * nc, st));
     if (gmap) HIPCHK(c, dev_to_host(c, gmap, dGm, sizeof(double) * nc, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    if (bad) return set_err(c, EIK_ERR_ARG, "GetObstMap: a surface index below -sZ (the reference raises IndexError)");
+    if (bad) return arm_obst_bad(c, bad);
     return EIK_OK;
 }
 
