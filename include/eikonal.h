@@ -149,13 +149,18 @@ typedef enum {
                                 order of equal T and so its nodeJoin / closed set, bit for bit; 0
                                 (default) = band cells at their final (2D: relaxed) values (GPU <=
                                 reference <= 1.03 x GPU), ties by node index / strict < T[start] */
-    EIK_OPT_WIDE = 20        /* fp32 2D persistent solves: which form of the kernel is launched
+    EIK_OPT_WIDE = 20,       /* fp32 2D persistent solves: which form of the kernel is launched
                                 (and the co-resident workgroup count that goes with it).  < 0
                                 (default) = by size: the 4-waves-per-SIMD form on maps of >= 16384
                                 tiles, else the narrow form; 0 = always the narrow form; 1 =
                                 always the 4-waves-per-SIMD form.  The pass cap, the bands and the
                                 dispatch batch keep their own defaults (EIK_OPT_PASSES, _PRIO,
                                 _PRIO_DISPATCH); fp64 solves ignore it.                          */
+    EIK_OPT_DIFF_LOADS = 21, /* the cost diff's loads (eik_cost_diff_dev, eik_fim2d_resolve_cost): 1
+                                (default) non-temporal, 0 plain; same results (tools/cost_diff_ab.py) */
+    EIK_OPT_DIFF_SHARE = 22  /* eik_fim2d_resolve_cost solves from scratch when more than this share
+                                of the raster's tiles changed; < 0 (default): the measured constant
+                                (DESIGN.md §3.15); >= 1: never                                      */
 } eik_option;
 
 typedef enum { EIK_MODE_LIST = 0, EIK_MODE_PERSISTENT = 1 } eik_mode;
@@ -472,6 +477,60 @@ int eik_tmap2d_update_seeds_f64(eik_ctx* ctx, const double* cost_new, double* T_
                                 const int64_t* seeds_old, const double* t0_old, int64_t K_old, const int64_t* seeds_new,
                                 const double* t0_new, int64_t K_new, const int64_t* rects, const int* kinds, int64_t K,
                                 int32_t* labels);
+
+/* Rectangle-free replanning (no reference counterpart): a device diff of two cost rasters
+ * names the rectangles and kinds that eik_fim2d_update needs, so the chain eik_costmap_dev ->
+ * eik_fim2d_resolve_cost -> walk never leaves the device.
+ *
+ * Per cell: changed when old != new as values (+0 equals -0, +inf equals +inf); raised when new > old
+ * (finite -> +inf is raised, +inf -> finite is lowered); invalid when new is NaN or < 0 (an invalid cell
+ * counts as changed).  Per solver tile of 64 x 64 cells: the bounding box of its changed cells.
+ * The rule from tiles to rectangles.  A changed tile's rectangle is its bounding box, of kind
+ * EIK_CHANGE_ANY if the tile has a raised cell, else EIK_CHANGE_LOWERED.  More than cap rectangles: the
+ * union per block of 2 x 2 tiles, aligned to the tile grid's origin -- the bounding box of the members,
+ * ANY if any member is ANY -- then 4 x 4, 8 x 8, ... until at most cap are left.  Rectangles are emitted
+ * in ascending (block row, block column).  The result is a deterministic function of the two rasters.
+ *
+ * What changed between two device rasters of one shape.  Synchronous (the records are read back).
+ * rects: cap x (x0, y0, x1, y1) half-open, kinds: cap, *K rectangles written (0: the rasters are equal).
+ * info[0] cells changed, [1] cells raised, [2] cells of d_new that are NaN or negative, [3] tiles
+ * changed, [4] block side in tiles after coarsening (1, 2, 4, ...; 0 when K == 0), [5] device time in
+ * microseconds.  1 <= cap <= 1024.  Invalid cells do not fail this call: info[2] reports them. */
+int eik_cost_diff_dev(eik_ctx* ctx, const void* d_old, const void* d_new, int dtype, int64_t H, int64_t W,
+                      int64_t* rects, int* kinds, int64_t cap, int64_t* K, int64_t info[6], void* stream);
+
+/* Re-solve for a new cost raster without naming what changed.  d_cost_new is diffed against the bound
+ * cost.  Then the solver is bound to d_cost_new (the old buffer is the caller's again: two buffers in
+ * ping-pong, e.g. eik_costmap_dev's output) and re-solved with the rectangles and kinds of the diff.
+ * A bound single goal goes through eik_fim2d_resolve.  A bound seed set goes through
+ * eik_fim2d_resolve_seeds with the list unchanged.  Synchronous.
+ *
+ * EIK_ERR_ARG with a message and nothing launched: everything eik_fim2d_update refuses (B > 1, ghost
+ * strips, a layered block, not the persistent mode, a solver never started or adopted, a last solve that
+ * did not converge), and d_cost_new == NULL.
+ * Invalid new costs (NaN or negative): EIK_ERR_ARG, the message names their count and the first such
+ * cell; nothing is rebound, no update is launched and T keeps its bits.
+ * Equal rasters: the solver is rebound, no update is queued, T keeps its bits, eik_fim2d_update_info is
+ * zero and the solver stays converged (the K == 0 contract of eik_fim2d_update).
+ * When the changed tiles, of either kind, are more than a share of the raster's tiles (DESIGN.md §3.15;
+ * EIK_OPT_DIFF_SHARE) and more than 16, the solver is rebound and solves from scratch with the bound goal
+ * or seed list (eik_fim2d_solve / eik_fim2d_solve_seeds on the new buffer); no rectangle list is built.
+ * Failures after the rebind are those of eik_fim2d_resolve: the bound T is INVALID until a solve from
+ * scratch (eik_fim2d_solve / eik_fim2d_solve_seeds on d_cost_new).
+ *
+ * eik_fim2d_diff_info  out[0..5]: info[0..5] of the last eik_fim2d_resolve_cost's diff, [6] 1 = it solved
+ *                      from scratch by the share rule, [7] rectangles passed on.
+ * Not covered: a windowed rebuild of the cost raster itself, B > 1, layered and 3D solvers, the
+ * bidirectional fronts. */
+int eik_fim2d_resolve_cost(eik_fim2d* fim, const void* d_cost_new, void* stream);
+int eik_fim2d_diff_info(eik_fim2d* fim, int64_t out[8]);
+
+/* Host buffers: both costs and T, the converged field of cost_old for the goal, go up; T comes back as the
+ * field of cost_new (adopt on cost_old, then eik_fim2d_resolve_cost, on the context's cached solver). */
+int eik_tmap2d_update_cost_f32(eik_ctx* ctx, const float* cost_old, const float* cost_new, float* T_inout,
+                               int64_t H, int64_t W, int64_t gx, int64_t gy);
+int eik_tmap2d_update_cost_f64(eik_ctx* ctx, const double* cost_old, const double* cost_new, double* T_inout,
+                               int64_t H, int64_t W, int64_t gx, int64_t gy);
 
 /* Live domain decomposition (no reference counterpart: the multi-GPU split of SURVEY.md §8(e)).
  * eik_fim2d_launch(fim, 1) starts ONE persistent launch on the bound stream and returns at once.

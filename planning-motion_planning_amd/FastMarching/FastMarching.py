@@ -198,6 +198,19 @@ def updateTmap(costMap, Tmap, goal, changed):
     return T.astype(np.float64, copy=False)
 
 
+def updateTmapFromCost(costMap, oldCostMap, Tmap, goal):
+    """No reference counterpart: the field computeTmap(costMap, goal) would return, from Tmap -- the
+    field computeTmap returned for oldCostMap.  The two cost maps are compared on the device, so no mask
+    or rectangle is needed; only the cells whose old value depended on a raised cell are solved again
+    (DESIGN.md §3.15).  The inputs are not modified; the result is float64."""
+    cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
+    old = np.ascontiguousarray(oldCostMap, dtype=_DTYPE)
+    if old.shape != cost.shape or np.shape(Tmap) != cost.shape:
+        raise ValueError(f"updateTmapFromCost: costMap {cost.shape}, oldCostMap {old.shape}, Tmap {np.shape(Tmap)}")
+    T = _ctx().tmap2d_update_cost(old, cost, np.ascontiguousarray(Tmap, dtype=_DTYPE), _node(goal), dtype=_DTYPE)
+    return T.astype(np.float64, copy=False)
+
+
 def biComputeTmap(costMap, goal, start):
     """FastMarching.py:114-162 -> (TmapG, TmapS, nodeJoin uint32[2]).  EIKONAL_EXACT_BAND=1: the
     reference's own band values and LIFO ties, bit for bit (EIK_OPT_EXACT_BAND, csrc/bidir_exact.hip;

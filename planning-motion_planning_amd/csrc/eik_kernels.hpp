@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cost_diff_rects.hpp"
 #include "seed_diff.hpp"
 
 namespace eik {
@@ -137,6 +138,17 @@ int replan_flood_resident(bool f64, int cus);
 hipError_t replan_reset(const Fim2dArgs& a, const ReplanArgs& r, bool f64, hipStream_t st);
 // edge-column copies and kVisited from a field the caller binds as converged
 hipError_t replan_adopt(const Fim2dArgs& a, bool f64, hipStream_t st);
+
+// What changed between two cost rasters of one shape (cost_diff.hip; the records and the
+// rule from records to rectangles: cost_diff_rects.hpp).  Plain grid launches, asynchronous on st.
+// tiles: rec[ty * ntx + tx] = the record of solver tile (tx, ty), every tile writes its own.  nt: the
+// non-temporal load form (EIK_OPT_DIFF_LOADS).  The 16-byte loads need both pointers and the row pitch
+// 16-byte aligned; anything else takes the one-cell-per-lane instantiation, chosen here per launch.
+hipError_t cost_diff_tiles(const void* d_old, const void* d_new, bool f64, int64_t H, int64_t W, int ntx, int nty,
+                           DiffRecord* rec, bool nt, hipStream_t st);
+// one workgroup: out[0] = the totals (a DiffHeader in a record's 32 bytes), out[1 ..] = the records of the
+// changed tiles in ascending tile index (out: 1 + tiles records)
+hipError_t cost_diff_compact(const DiffRecord* rec, int tiles, DiffRecord* out, hipStream_t st);
 
 // Multi-source solves (seeds.hip): a seed set with start values, and the nearest-seed labels.
 constexpr int64_t kMaxSeeds = 1ll << 24;

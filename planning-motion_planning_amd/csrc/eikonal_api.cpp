@@ -227,6 +227,16 @@ struct eik_ctx {
     CopyPool* pool = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t e3[2] = {nullptr, nullptr};
+    // the cost diff (cost_diff.hip): every tile's record, the totals + the changed tiles'
+    // list, the list's pinned copy (1 + max(kMaxRects, tiles) records) and the kernels' timing events
+    DevBuf diff_rec, diff_out, cost2;  // (cost2: the host entries' old cost)
+    DiffRecord* h_diff = nullptr;
+    int64_t h_diff_cap = 0;
+    hipEvent_t ev_diff[2] = {nullptr, nullptr};
+    // EIK_OPT_DIFF_LOADS: non-temporal loads by default -- 16384^2 fp64 0.75-0.77 -> 0.66-0.71 ms, 4096^2 fp64
+    // 0.057-0.066 -> 0.049-0.062 ms, fp32 equal (profiles/cost_diff_ab.log)
+    bool diff_nt = true;
+    double diff_share = -1.0;          // EIK_OPT_DIFF_SHARE (< 0: kDiffFullShare)
     SeedStage lab_seeds;               // eik_labels2d_dev: its seeds, and its scratch (parents | pass flags)
     DevBuf lab_work, lab_out;          // (lab_out: the host entries' device labels)
     std::vector<DescBlock> desc;       // batched paths: descriptor blocks in flight or free (stage_desc)
@@ -272,6 +282,7 @@ struct eik_fim2d {
     bool rp_timed = false, rp_fallback = false;  // events recorded; the last resolve ended in a full solve
     int flood_grid = 0;                  // co-resident workgroups of the flood kernel
     int persist_grid = 0;                // co-resident workgroups of the persistent kernel
+    int64_t diff_info[8] = {};           // eik_fim2d_diff_info: of the last eik_fim2d_resolve_cost
     bool persist_wide = false;           // ... of which form (EIK_OPT_WIDE can change it between solves)
     // live domain decomposition: hold word on the device, mailbox of the halo agent on the host
     DevBuf hold;
@@ -473,6 +484,9 @@ void eik_destroy(eik_ctx* c) {
         if (b.h) (void)hipHostFree(b.h);
         if (b.d) (void)hipFree(b.d);
     }
+    if (c->h_diff) (void)hipHostFree(c->h_diff);
+    for (hipEvent_t e : c->ev_diff)
+        if (e) (void)hipEventDestroy(e);
     if (c->lab_seeds.ev) (void)hipEventSynchronize(c->lab_seeds.ev);
     c->lab_seeds.release();
     c->pool = nullptr;  // (the process-wide pool stays)
@@ -510,6 +524,8 @@ int eik_set_option(eik_ctx* c, int opt, double v) {
         case EIK_OPT_PATH_LOOP: c->path_loop = std::max(0, std::min(4, (int)v)); break;
         case EIK_OPT_EXACT_BAND: c->exact_band = v != 0; break;
         case EIK_OPT_WIDE: c->wide = v < 0 ? -1 : v != 0 ? 1 : 0; break;
+        case EIK_OPT_DIFF_LOADS: c->diff_nt = v != 0; break;
+        case EIK_OPT_DIFF_SHARE: c->diff_share = v < 0 ? -1.0 : v; break;
         case EIK_OPT_FRONTS_CAP: c->fronts_cap = v <= 0 ? 0.0 : v == 1 ? kFrontsMargin : std::max(1.0, v); break;
         default: return set_err(c, EIK_ERR_ARG, "unknown option %d", opt);
     }
@@ -1488,6 +1504,205 @@ int eik_fim2d_update_info(eik_fim2d* f, int64_t out[6]) {
     return EIK_OK;
 }
 
+// ---- rectangle-free replanning: the device cost diff feeding the re-solve (cost_diff.hip)
+// eik_fim2d_resolve_cost solves from scratch when more than this share of the raster's tiles changed: the
+// largest measured share at which the update still beat the full solve by more than the full solve's own
+// run-to-run spread (the share table; profiles/cost_diff_ab.log).
+constexpr double kDiffFullShare = 1.0 / 64.0;
+// ... and more than this many tiles: on a raster of a few tiles one changed tile is already above any share,
+// and the table's smallest raster has 4096 tiles (one 4 x 4 block of tiles, a 256^2 raster, always updates)
+constexpr int64_t kDiffMinTiles = 16;
+
+// Both kernels on st, the totals and the first kMaxRects list entries back in one pinned copy, then one
+// synchronisation: *hdr = the totals, c->h_diff[1 ..] the list's head, *us the kernels' device time.
+static int diff_run(eik_ctx* c, const void* d_old, const void* d_new, bool f64, int64_t H, int64_t W, hipStream_t st,
+                    DiffHeader* hdr, int64_t* us) {
+    const int64_t ntx = (W + kTile - 1) / kTile, nty = (H + kTile - 1) / kTile, tiles = ntx * nty;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->diff_rec.ensure(sizeof(DiffRecord) * (size_t)tiles));
+    HIPCHK(c, c->diff_out.ensure(sizeof(DiffRecord) * (size_t)(1 + tiles)));
+    const int64_t want = 1 + std::max<int64_t>(kMaxRects, tiles);
+    if (c->h_diff_cap < want) {
+        if (c->h_diff) (void)hipHostFree(c->h_diff);
+        c->h_diff = nullptr;
+        c->h_diff_cap = 0;
+        HIPCHK(c, hipHostMalloc((void**)&c->h_diff, sizeof(DiffRecord) * (size_t)want));
+        c->h_diff_cap = want;
+    }
+    for (hipEvent_t& ev : c->ev_diff)
+        if (!ev) HIPCHK(c, hipEventCreate(&ev));
+    HIPCHK(c, hipEventRecord(c->ev_diff[0], st));
+    HIPCHK(c, cost_diff_tiles(d_old, d_new, f64, H, W, (int)ntx, (int)nty, (DiffRecord*)c->diff_rec.p, c->diff_nt, st));
+    HIPCHK(c, cost_diff_compact((const DiffRecord*)c->diff_rec.p, (int)tiles, (DiffRecord*)c->diff_out.p, st));
+    HIPCHK(c, hipEventRecord(c->ev_diff[1], st));
+    // (entries past the changed tiles are stale words of an earlier call: only hdr->tiles of them are read)
+    const int64_t head = 1 + std::min<int64_t>(kMaxRects, tiles);
+    HIPCHK(c, hipMemcpyAsync(c->h_diff, c->diff_out.p, sizeof(DiffRecord) * (size_t)head, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(hdr, c->h_diff, sizeof *hdr);
+    float ms = 0.f;
+    *us = hipEventElapsedTime(&ms, c->ev_diff[0], c->ev_diff[1]) == hipSuccess ? (int64_t)(ms * 1000.0f + 0.5f) : 0;
+    return EIK_OK;
+}
+
+// the whole list of n changed tiles in c->h_diff[1 ..]: a second read-back only past the first kMaxRects
+static int diff_list(eik_ctx* c, int64_t n, hipStream_t st, const DiffRecord** list) {
+    if (n > kMaxRects) {
+        HIPCHK(c, hipMemcpyAsync(c->h_diff + 1 + kMaxRects, (const DiffRecord*)c->diff_out.p + 1 + kMaxRects,
+                                 sizeof(DiffRecord) * (size_t)(n - kMaxRects), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+    }
+    *list = c->h_diff + 1;
+    return EIK_OK;
+}
+
+int eik_cost_diff_dev(eik_ctx* c, const void* d_old, const void* d_new, int dtype, int64_t H, int64_t W, int64_t* rects,
+                      int* kinds, int64_t cap, int64_t* K, int64_t info[6], void* stream) {
+    if (!c) return EIK_ERR_ARG;
+    const char* who = "eik_cost_diff_dev";
+    if (!d_old || !d_new || !rects || !kinds || !K || !info) return set_err(c, EIK_ERR_ARG, "%s: NULL argument", who);
+    if (dtype != EIK_F32 && dtype != EIK_F64) return set_err(c, EIK_ERR_ARG, "%s: bad dtype %d", who, dtype);
+    if (H < 1 || W < 1 || H >= (1ll << 31) - kTile || W >= (1ll << 31) - kTile ||
+        ((H + kTile - 1) / kTile) * ((W + kTile - 1) / kTile) >= (1ll << 31) - 8)
+        return set_err(c, EIK_ERR_ARG, "%s: bad shape %ld x %ld", who, (long)H, (long)W);
+    if (cap < 1 || cap > kMaxRects) return set_err(c, EIK_ERR_ARG, "%s: cap = %ld outside [1, %d]", who, (long)cap, kMaxRects);
+    *K = 0;
+    DiffHeader h{};
+    int64_t us = 0;
+    hipStream_t st = (hipStream_t)stream;
+    int rc = diff_run(c, d_old, d_new, dtype == EIK_F64, H, W, st, &h, &us);
+    if (rc) return rc;
+    int side = 0;
+    if (h.tiles > 0) {
+        const DiffRecord* list = nullptr;
+        rc = diff_list(c, (int64_t)h.tiles, st, &list);
+        if (rc) return rc;
+        std::vector<DiffRect> out;
+        side = diff_rects(list, (int64_t)h.tiles, (int)((W + kTile - 1) / kTile), cap, out);
+        for (size_t k = 0; k < out.size(); ++k) {
+            rects[4 * k] = out[k].x0;
+            rects[4 * k + 1] = out[k].y0;
+            rects[4 * k + 2] = out[k].x1;
+            rects[4 * k + 3] = out[k].y1;
+            kinds[k] = out[k].kind;
+        }
+        *K = (int64_t)out.size();
+    }
+    info[0] = (int64_t)h.changed;
+    info[1] = (int64_t)h.raised;
+    info[2] = (int64_t)h.invalid;
+    info[3] = (int64_t)h.tiles;
+    info[4] = side;
+    info[5] = us;
+    return EIK_OK;
+}
+
+// the error of an invalid new cost: its count and the first such cell (row-major) of the lowest changed
+// tile holding one, read back from that tile alone
+static int diff_invalid_error(eik_fim2d* f, const void* d_new, const DiffHeader& h, hipStream_t st) {
+    eik_ctx* c = f->ctx;
+    const char* who = "eik_fim2d_resolve_cost";
+    const DiffRecord* list = nullptr;
+    int rc = diff_list(c, (int64_t)h.tiles, st, &list);
+    if (rc) return rc;
+    for (uint64_t i = 0; i < h.tiles; ++i) {
+        if (!list[i].invalid) continue;
+        const int64_t x0 = (int64_t)(list[i].tile % f->a.ntx) * kTile, y0 = (int64_t)(list[i].tile / f->a.ntx) * kTile;
+        const int64_t w = std::min<int64_t>(kTile, f->W - x0), hh = std::min<int64_t>(kTile, f->H - y0);
+        const size_t cell = f->f64 ? 8 : 4;
+        std::vector<char> buf(cell * (size_t)(w * hh));
+        HIPCHK(c, hipMemcpy2DAsync(buf.data(), cell * w, (const char*)d_new + cell * (size_t)(y0 * f->W + x0), cell * f->W,
+                                   cell * w, (size_t)hh, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        for (int64_t k = 0; k < w * hh; ++k) {
+            const double v = f->f64 ? ((const double*)buf.data())[k] : (double)((const float*)buf.data())[k];
+            if (!(v >= 0.0))
+                return set_err(c, EIK_ERR_ARG, "%s: %llu cells of the new cost are NaN or negative, cost[%ld][%ld] = %g among "
+                                               "them: costs must be >= 0 or +inf; nothing was rebound",
+                               who, (unsigned long long)h.invalid, (long)(y0 + k / w), (long)(x0 + k % w), v);
+        }
+    }
+    return set_err(c, EIK_ERR_ARG, "%s: %llu cells of the new cost are NaN or negative: costs must be >= 0 or +inf; nothing was "
+                                   "rebound", who, (unsigned long long)h.invalid);
+}
+
+int eik_fim2d_resolve_cost(eik_fim2d* f, const void* d_cost_new, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    const char* who = "eik_fim2d_resolve_cost";
+    if (!d_cost_new) return set_err(c, EIK_ERR_ARG, "%s: d_cost_new is NULL", who);
+    // what eik_fim2d_update / eik_fim2d_update_seeds refuse, before anything is launched or rebound
+    int rc = replan_gate(f, who);
+    if (rc) return rc;
+    if (!f->started || !f->a.cost || !f->a.T) return set_err(c, EIK_ERR_ARG, "%s: the solver was never started or adopted", who);
+    if (f->seeded && f->bound.empty()) return set_err(c, EIK_ERR_ARG, "%s: the bound seed list is empty", who);
+    if (f->a.mode != kModePersistent) return set_err(c, EIK_ERR_ARG, "%s: the bound solve did not run in the persistent mode", who);
+    if (f->last_active != 0) return set_err(c, EIK_ERR_ARG, "%s: the last solve did not end converged (0 active tiles)", who);
+    hipStream_t st = (hipStream_t)stream;
+    DiffHeader h{};
+    int64_t us = 0;
+    rc = diff_run(c, f->a.cost, d_cost_new, f->f64, f->H, f->W, st, &h, &us);
+    if (rc) return rc;
+    int64_t* di = f->diff_info;
+    di[0] = (int64_t)h.changed;
+    di[1] = (int64_t)h.raised;
+    di[2] = (int64_t)h.invalid;
+    di[3] = (int64_t)h.tiles;
+    di[4] = 0;
+    di[5] = us;
+    di[6] = di[7] = 0;
+    if (h.invalid > 0) return diff_invalid_error(f, d_cost_new, h, st);
+    const double share = c->diff_share >= 0 ? c->diff_share : kDiffFullShare;
+    void* d_T = f->a.T;
+    if ((int64_t)h.tiles > kDiffMinTiles && (double)h.tiles > share * (double)f->a.capacity) {
+        // the share rule: most of the raster changed, the solve from scratch is the faster one (no list is built)
+        di[6] = 1;
+        if (!f->seeded) {
+            const int64_t g[2] = {f->h_goals[0], f->h_goals[1]};
+            return eik_fim2d_solve(f, d_cost_new, d_T, g, stream);
+        }
+        const std::vector<SeedDesc> b = f->bound;
+        std::vector<int64_t> s(2 * b.size());
+        std::vector<double> t(b.size());
+        for (size_t k = 0; k < b.size(); ++k) {
+            s[2 * k] = b[k].x;
+            s[2 * k + 1] = b[k].y;
+            t[k] = b[k].t0;
+        }
+        return eik_fim2d_solve_seeds(f, d_cost_new, d_T, s.data(), t.data(), nullptr, (int64_t)b.size(), stream);
+    }
+    std::vector<int64_t> rects;
+    std::vector<int> kinds;
+    if (h.tiles > 0) {
+        const DiffRecord* list = nullptr;
+        rc = diff_list(c, (int64_t)h.tiles, st, &list);
+        if (rc) return rc;
+        std::vector<DiffRect> out;
+        di[4] = diff_rects(list, (int64_t)h.tiles, f->a.ntx, kMaxRects, out);
+        rects.resize(4 * out.size());
+        kinds.resize(out.size());
+        for (size_t k = 0; k < out.size(); ++k) {
+            rects[4 * k] = out[k].x0;
+            rects[4 * k + 1] = out[k].y0;
+            rects[4 * k + 2] = out[k].x1;
+            rects[4 * k + 3] = out[k].y1;
+            kinds[k] = out[k].kind;
+        }
+    }
+    const int64_t K = (int64_t)kinds.size();
+    di[7] = K;
+    // the rebind: the update path reads the cost through f->a.cost (K == 0, equal rasters: its no-op contract)
+    f->a.cost = d_cost_new;
+    if (f->seeded) return eik_fim2d_resolve_seeds(f, K ? rects.data() : nullptr, K ? kinds.data() : nullptr, K, nullptr, nullptr, 0, stream);
+    return eik_fim2d_resolve(f, K ? rects.data() : nullptr, K ? kinds.data() : nullptr, K, stream);
+}
+
+int eik_fim2d_diff_info(eik_fim2d* f, int64_t out[8]) {
+    if (!f || !out) return EIK_ERR_ARG;
+    memcpy(out, f->diff_info, sizeof f->diff_info);
+    return EIK_OK;
+}
+
 int eik_fim2d_pack_edges(eik_fim2d* f, void* n, void* s, void* w, void* e) {
     if (!f || !f->started) return EIK_ERR_ARG;
     if (f->lnl)  // a layered block: nl values per edge cell
@@ -1872,6 +2087,38 @@ static int tmap_update_host(eik_ctx* c, const R* cost, R* T, int64_t H, int64_t 
     return EIK_OK;
 }
 
+// both costs and the converged field of cost_old go up; adopt on cost_old, then the diff names what changed
+template <typename R>
+static int tmap_update_cost_host(eik_ctx* c, const R* cost_old, const R* cost_new, R* T, int64_t H, int64_t W, int64_t gx,
+                                 int64_t gy) {
+    if (!c) return EIK_ERR_ARG;
+    const char* who = "eik_tmap2d_update_cost";
+    if (!cost_old || !cost_new || !T)
+        return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !cost_old ? "cost_old" : !cost_new ? "cost_new" : "T_inout");
+    if (H < 1 || W < 1) return set_err(c, EIK_ERR_ARG, "%s: bad shape %ld x %ld", who, (long)H, (long)W);
+    if (gx < 0 || gy < 0 || gx >= W || gy >= H)
+        return set_err(c, EIK_ERR_ARG, "%s: goal (%ld, %ld) outside %ldx%ld", who, (long)gx, (long)gy, (long)H, (long)W);
+    const int64_t n = H * W;
+    HIPCHK(c, hipSetDevice(c->device));
+    eik_fim2d* f = nullptr;
+    int rc = get_solver(c, 1, H, W, sizeof(R) == 8 ? EIK_F64 : EIK_F32, &f);
+    if (!rc) rc = replan_gate(f, who);
+    if (rc) return rc;
+    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
+    HIPCHK(c, c->cost2.ensure(sizeof(R) * n));
+    HIPCHK(c, c->T.ensure(sizeof(R) * n));
+    HIPCHK(c, host_to_dev(c, c->cost2.p, cost_old, sizeof(R) * n, c->stream));
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost_new, sizeof(R) * n, c->stream));
+    HIPCHK(c, host_to_dev(c, c->T.p, T, sizeof(R) * n, c->stream));
+    const int64_t g[2] = {gx, gy};
+    rc = eik_fim2d_adopt(f, c->cost2.p, c->T.p, g, c->stream);
+    if (!rc) rc = eik_fim2d_resolve_cost(f, c->cost.p, c->stream);  // (it checks cost_new: NaN or negative is EIK_ERR_ARG)
+    if (rc) return rc;
+    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
 // one map from a seed set on the cached solver; labels (optional) from the field while it is on the device
 template <typename R>
 static int tmap_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, const int64_t* seeds, const double* t0,
@@ -1978,6 +2225,16 @@ int eik_tmap2d_update_f32(eik_ctx* c, const float* cost_new, float* T, int64_t H
 int eik_tmap2d_update_f64(eik_ctx* c, const double* cost_new, double* T, int64_t H, int64_t W, int64_t gx, int64_t gy,
                           const int64_t* rects, const int* kinds, int64_t K) {
     return tmap_update_host<double>(c, cost_new, T, H, W, gx, gy, rects, kinds, K);
+}
+
+int eik_tmap2d_update_cost_f32(eik_ctx* c, const float* cost_old, const float* cost_new, float* T, int64_t H, int64_t W,
+                               int64_t gx, int64_t gy) {
+    return tmap_update_cost_host<float>(c, cost_old, cost_new, T, H, W, gx, gy);
+}
+
+int eik_tmap2d_update_cost_f64(eik_ctx* c, const double* cost_old, const double* cost_new, double* T, int64_t H, int64_t W,
+                               int64_t gx, int64_t gy) {
+    return tmap_update_cost_host<double>(c, cost_old, cost_new, T, H, W, gx, gy);
 }
 
 int eik_tmap2d_f32(eik_ctx* c, const float* cost, int64_t H, int64_t W, int64_t gx, int64_t gy, float* T) {

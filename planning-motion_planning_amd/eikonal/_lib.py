@@ -16,7 +16,7 @@ PATH_STUCK = 3  # the safe walker only (path2d_safe*): no lower neighbour, or ou
 OPT_MAX_ROUNDS, OPT_SYNC_EVERY, OPT_TIMING, OPT_GRID, OPT_TOL, OPT_DELTA = 0, 1, 2, 3, 4, 5
 OPT_MODE, OPT_QTIMEOUT, OPT_MAX_VISITS, OPT_PASSES, OPT_FRESH_FIRST, OPT_SCHED, OPT_PATH_LOOP = 6, 7, 8, 9, 10, 11, 12
 OPT_FRONTS_CAP, OPT_LIVE_PACK, OPT_PRIO, OPT_LAYER_PLANAR, OPT_PRIO_RING, OPT_PRIO_DISPATCH = 13, 14, 15, 16, 17, 18
-OPT_EXACT_BAND, OPT_WIDE = 19, 20
+OPT_EXACT_BAND, OPT_WIDE, OPT_DIFF_LOADS, OPT_DIFF_SHARE = 19, 20, 21, 22
 MODE_LIST, MODE_PERSISTENT = 0, 1
 
 i64 = C.c_int64
@@ -232,6 +232,12 @@ def lib():
         L.eik_fim2d_resolve_seeds.argtypes = [vp, vp, vp, i64, vp, vp, i64, vp]
         L.eik_tmap2d_update_seeds_f32.argtypes = [vp, _f32p, _f32p, i64, i64, _i64p, vp, i64, vp, vp, i64, vp, vp, i64, vp]
         L.eik_tmap2d_update_seeds_f64.argtypes = [vp, _f64p, _f64p, i64, i64, _i64p, vp, i64, vp, vp, i64, vp, vp, i64, vp]
+        # rectangle-free replanning: the device cost diff and the re-solve it feeds
+        L.eik_cost_diff_dev.argtypes = [vp, vp, vp, C.c_int, i64, i64, _i64p, _i32p, i64, P(i64), _i64p, vp]
+        L.eik_fim2d_resolve_cost.argtypes = [vp, vp, vp]
+        L.eik_fim2d_diff_info.argtypes = [vp, _i64p]
+        L.eik_tmap2d_update_cost_f32.argtypes = [vp, _f32p, _f32p, _f32p, i64, i64, i64, i64]
+        L.eik_tmap2d_update_cost_f64.argtypes = [vp, _f64p, _f64p, _f64p, i64, i64, i64, i64]
         _lib = L
         return L
 
@@ -295,6 +301,8 @@ EXPORTED = [
     "eik_tmap2d_seeds_f64",
     "eik_fim2d_adopt_seeds", "eik_fim2d_update_seeds", "eik_fim2d_resolve_seeds", "eik_tmap2d_update_seeds_f32",
     "eik_tmap2d_update_seeds_f64",
+    "eik_cost_diff_dev", "eik_fim2d_resolve_cost", "eik_fim2d_diff_info", "eik_tmap2d_update_cost_f32",
+    "eik_tmap2d_update_cost_f64",
 ]
 
 
@@ -421,6 +429,37 @@ class Context:
         self._chk(fn(self._h, cost, out, H, W, int(goal[0]), int(goal[1]), r.ctypes.data if K else None,
                      k.ctypes.data if k is not None and K else None, K))
         return out
+
+    def tmap2d_update_cost(self, cost_old, cost_new, T, goal, dtype=np.float64):
+        """The field of `cost_new` from T, the converged field of `cost_old` for `goal`: the two costs are
+        compared on the device and only what depended on the raised cells is solved again
+        (eik_tmap2d_update_cost_*).  No rectangles are named.  The inputs are not modified."""
+        old = np.ascontiguousarray(cost_old, dtype=dtype)
+        new = np.ascontiguousarray(cost_new, dtype=dtype)
+        H, W = new.shape
+        if old.shape != new.shape or np.shape(T) != new.shape:
+            raise ValueError(f"tmap2d_update_cost: cost_old {old.shape}, cost_new {new.shape}, T {np.shape(T)}")
+        out = result_empty(new.shape, new.dtype)
+        out[...] = T
+        fn = lib().eik_tmap2d_update_cost_f64 if new.dtype == np.float64 else lib().eik_tmap2d_update_cost_f32
+        self._chk(fn(self._h, old, new, out, H, W, int(goal[0]), int(goal[1])))
+        return out
+
+    def cost_diff(self, d_old, d_new, dtype, H, W, cap=1024, stream=None):
+        """What changed between two device rasters (addresses) of H x W cells of `dtype` (EIK_F32 / EIK_F64),
+        as eik_fim2d_update takes it (eik_cost_diff_dev): (rects int64 [K][4] half-open, kinds int32 [K],
+        info).  At most `cap` rectangles: more changed tiles are boxed per 2 x 2, 4 x 4, ... tiles."""
+        cap = int(cap)
+        if cap < 1:
+            raise ValueError(f"cost_diff: cap = {cap}")
+        rects = np.zeros((cap, 4), np.int64)
+        kinds = np.zeros(cap, np.int32)
+        K = i64(0)
+        info = np.zeros(6, np.int64)
+        self._chk(lib().eik_cost_diff_dev(self._h, d_old, d_new, int(dtype), int(H), int(W), rects.reshape(-1), kinds, cap,
+                                          C.byref(K), info, stream))
+        names = ("cells_changed", "cells_raised", "cells_invalid", "tiles_changed", "block_side", "device_us")
+        return rects[: K.value].copy(), kinds[: K.value].copy(), dict(zip(names, (int(v) for v in info)))
 
     def tmap2d_seeds(self, cost, seeds, t0=None, dtype=np.float64, labels=False):
         """The field of a seed set (eik_tmap2d_seeds_*): seeds K x (x, y), t0 their start values (None: all
@@ -889,6 +928,17 @@ class Fim2d:
 
     def resolve_seeds(self, rects, kinds=None, seeds=None, t0=None, stream=None):
         self._update_seeds(lib().eik_fim2d_resolve_seeds, rects, kinds, seeds, t0, stream)
+
+    def resolve_cost(self, d_cost_new, stream=None):
+        """the re-solve for a new cost raster (a device address) without naming what changed: it is diffed
+        against the bound cost, the solver is bound to it and re-solved (eik_fim2d_resolve_cost)"""
+        self.ctx._chk(lib().eik_fim2d_resolve_cost(self._h, d_cost_new, stream))
+
+    def diff_info(self):
+        o = np.zeros(8, np.int64)
+        self.ctx._chk(lib().eik_fim2d_diff_info(self._h, o))
+        return dict(zip(("cells_changed", "cells_raised", "cells_invalid", "tiles_changed", "block_side", "device_us",
+                         "solved_from_scratch", "rects"), (int(v) for v in o)))
 
     def update_info(self):
         o = np.zeros(6, np.int64)
