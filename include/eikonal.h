@@ -376,7 +376,9 @@ int eik_tmap2d_update_f64(eik_ctx* ctx, const double* cost_new, double* T_inout,
  * eik_tmap2d_seeds_*) return EIK_ERR_ARG ("the bound solve has a seed set") until an eik_fim2d_start /
  * eik_fim2d_solve / eik_fim2d_adopt (any single-goal host solve on the context) binds a single-goal
  * solve again.
- * Not covered: 3D and layered solves, the bidirectional fronts, a seeded eik_plan2d_batch. */
+ * Not covered: the layered solver, the bidirectional fronts, a seeded eik_plan2d_batch.  3D volumes:
+ * eik_fim3d_solve_seeds below (one volume on the general 3D solver; no 3D replanning, no B > 1, no
+ * early exit with a seed set). */
 int eik_fim2d_start_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
                           const int32_t* map_of, int64_t K, void* stream);
 int eik_fim2d_solve_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
@@ -458,7 +460,8 @@ int eik_tmap2d_seeds_f64(eik_ctx* ctx, const double* cost, int64_t H, int64_t W,
  * bound T is INVALID -- it may hold sign-marked (negative) values and a partly reset cone, and spared
  * roots that were lifted for the invalidation may read +inf.  Solve from scratch
  * (eik_fim2d_solve_seeds) before the field or a further update is used.
- * Not covered: B > 1, layered and 3D solves, a seeded eik_plan2d_batch. */
+ * Not covered: B > 1, the layered solver, 3D replanning (eik_fim3d_solve_seeds solves from scratch), a
+ * seeded eik_plan2d_batch. */
 int eik_fim2d_adopt_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
                           int64_t Ks, void* stream);
 int eik_fim2d_update_seeds(eik_fim2d* fim, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
@@ -670,6 +673,53 @@ int eik_plan2d_batch_f32(eik_ctx* ctx, const float* cost, int64_t B, int64_t H, 
  * eik_get_stats). */
 int eik_fim3d_solve(eik_ctx* ctx, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
                     const int64_t goal[3], void* stream);
+
+/* Goal sets for 3D solves (no reference counterpart): the field of a SET of K seeds in
+ * one volume, seed k at cell (x, y, z) with start value t0[k] >= 0,
+ *     T = min_k (t0[k] + cost-to-go from seed k)
+ * as the solver's own discrete fixed point (below the pointwise minimum of K single-goal fields, as in
+ * 2D above), and the nearest-goal label of every cell.  Several admissible final arm waypoints, each with
+ * a penalty: one field and the partition, not K solves.
+ * Two seeds may name one cell (the lower t0 holds); a seed that another seed's wave undercuts is
+ * dominated (T there ends below its t0).  A seed on a +inf-cost cell keeps its t0.
+ *
+ * seeds: K x (x, y, z), host.  t0: K host doubles, rounded to dtype, or NULL (all 0).  The host arrays
+ * are read before the call returns and go to the device in stream order through a pinned block.
+ *
+ * eik_fim3d_solve_seeds  synchronous, like eik_fim3d_solve.  It always runs on the general 3D solver --
+ *                        the persistent driver while the volume is under 4 GiB and the context is in
+ *                        persistent mode, else the list driver -- also for the few-layer volumes that
+ *                        eik_fim3d_solve gives to the layered solver.  eik_get_stats, EIK_OPT_PASSES,
+ *                        EIK_OPT_GRID, EIK_OPT_QTIMEOUT and EIK_OPT_MAX_VISITS behave as in eik_fim3d_solve.
+ * eik_labels3d_dev       the labels of a converged field d_T of H x W x L cells in dtype (fewer than 2^31
+ *                        cells) for the seed list that produced it -> d_label, int32 [H][W][L], device.
+ *                        Asynchronous on `stream`, no read-back.  The context owns the scratch (shared
+ *                        with eik_labels2d_dev): calls on one stream queue up, calls on different streams
+ *                        must not overlap.
+ * The label rule is eik_labels2d_dev's with 6 neighbours:
+ *   Root.   Cell c is a root with label k when seed k lies on c and T[c] == (R)t0_k bit for bit.  Of
+ *           several such k, the lowest wins.  A seed that another seed's wave undercut is not a root.
+ *   Parent. Otherwise, the parent of a finite cell is its 6-neighbour with the smallest T strictly
+ *           below T[c].  Among equal candidates the first in the order x-1, x+1, y-1, y+1, z-1, z+1
+ *           wins.  The label of c is the label of its parent.
+ *   Unlabelled cells.  label = -1 for: a cell with T = +inf; a finite non-root cell with no strictly
+ *           lower neighbour (a zero-cost plateau, or fp32 rounding of T + c to T); everything whose
+ *           parent chain ends in such a cell.
+ *
+ * EIK_ERR_ARG, with a message naming the offending index and nothing launched: K < 1 or K > 2^24, a
+ * NULL pointer, a seed outside the volume, a t0 that is negative, NaN or +inf or (fp32) rounds to +inf,
+ * H, W or L < 1.
+ * Not covered: 3D replanning, B > 1 volumes per call, the layered solver, early exit with a seed set. */
+int eik_fim3d_solve_seeds(eik_ctx* ctx, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
+                          const int64_t* seeds, const double* t0, int64_t K, void* stream);
+int eik_labels3d_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                     const double* t0, int64_t K, int32_t* d_label, void* stream);
+
+/* Host buffers, one volume: cost in, the seeded field T and (labels != NULL) its labels out. */
+int eik_tmap3d_seeds_f32(eik_ctx* ctx, const float* cost, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                         const double* t0, int64_t K, float* T, int32_t* labels);
+int eik_tmap3d_seeds_f64(eik_ctx* ctx, const double* cost, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                         const double* t0, int64_t K, double* T, int32_t* labels);
 
 /* FastMarching3D.computeTmap's early exit at `start` (:141) on device buffers: d_T (a converged
  * full field from eik_fim3d_solve) -> d_Te (a different buffer), async on `stream`. */

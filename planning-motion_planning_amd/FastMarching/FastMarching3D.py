@@ -3,6 +3,10 @@
   computeTmap(costMap, goal, start)   FastMarching3D.py:126-145 -> GPU 3D block-FIM + early exit
   getPathGDM(T, init, end, tau)       FastMarching3D.py:198-271 -> GPU path kernel
   getPathsGDM(T, inits, end, tau)     no reference counterpart: many getPathGDM walks in one launch
+  computeTmapMulti(costMap, goals, offsets, labels)             no reference counterpart: the field of a
+                                      goal SET with start values, and every cell's nearest goal
+  getPathsToNearest(T, labels, goals, inits, tau)               no reference counterpart: every start
+                                      walks to the goal its cell belongs to, in one launch
 Host-side scalar/list helpers keep their reference semantics: updateNode :19-101,
 sumlist :103-107, getMinNB :109-123, interpolatePoint :275-314.
 
@@ -155,4 +159,63 @@ def getPathsGDM(totalCostMap, initWaypoints, endWaypoint, tau):
     bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
     if bad:
         raise IndexError(f"getPathsGDM (3D): the descent of path {bad[0]} left the volume (getPathGDM raises here too)")
+    return [path for path, _ in res]
+
+
+def _goal_list(goals, shape):
+    """goals as a (K, 3) int64 array of nodes (x, y, z): a list of nodes, or a boolean mask of `shape`
+    (cost[y, x, z]) whose True cells are the seeds in row-major order"""
+    g = np.asarray(goals)
+    if g.dtype == bool:
+        if g.shape != tuple(shape):
+            raise ValueError(f"computeTmapMulti: the mask has shape {g.shape}, costMap {tuple(shape)}")
+        ys, xs, zs = np.nonzero(g)  # row-major
+        return np.stack([xs, ys, zs], axis=1).astype(np.int64)
+    if g.ndim != 2 or g.shape[1] < 3:
+        raise ValueError(f"computeTmapMulti: goals must be K nodes (x, y, z) or a boolean mask, not shape {g.shape}")
+    return np.ascontiguousarray(g[:, :3], dtype=np.int64)
+
+
+def computeTmapMulti(costMap, goals, offsets=None, labels=False):
+    """No reference counterpart: the arrival-time field of a goal SET in a volume, min over the goals of
+    (offset + cost-to-go), solved as one problem on the general 3D solver.  goals: K
+    nodes (x, y, z), or a boolean mask of costMap's shape (its True cells, row-major); offsets: K start
+    values >= 0 (None: all 0).  Returns the full field T (float64), or with labels=True (T, labels):
+    int32, the index into goals of the goal each cell belongs to, -1 for unreached cells."""
+    cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
+    if cost.ndim != 3:
+        raise ValueError(f"computeTmapMulti: costMap must be a volume, not shape {cost.shape}")
+    g = _goal_list(goals, cost.shape)
+    if len(g) == 0:
+        raise ValueError("computeTmapMulti: no goal")
+    res = _ctx().tmap3d_seeds(cost, g, offsets, dtype=_DTYPE, labels=labels)
+    if labels:
+        return res[0].astype(np.float64, copy=False), res[1]
+    return res.astype(np.float64, copy=False)
+
+
+def getPathsToNearest(totalCostMap, labels, goals, initWaypoints, tau):
+    """No reference counterpart: from every row of initWaypoints (P, 3), getPathGDM to the goal its cell
+    belongs to -- goals[labels[node(start)]], with (totalCostMap, labels) from computeTmapMulti(...,
+    labels=True) and the same goals -- in one launch -> a list of P (K, 3) float64 paths.  ValueError
+    names a start whose cell has no label (-1: unreached); IndexError as getPathsGDM."""
+    T = np.ascontiguousarray(totalCostMap, dtype=np.float64)
+    lab = np.asarray(labels)
+    if T.ndim != 3 or lab.shape != T.shape:
+        raise ValueError(f"getPathsToNearest: labels have shape {lab.shape}, the field {T.shape}")
+    g = _goal_list(goals, T.shape)
+    inits = np.asarray(initWaypoints, dtype=np.float64)
+    inits = inits.reshape(-1, inits.shape[-1])[:, :3]
+    ends = np.empty_like(inits)
+    for p, s in enumerate(inits):
+        x, y, z = int(s[0]), int(s[1]), int(s[2])
+        inside = 0 <= x < T.shape[1] and 0 <= y < T.shape[0] and 0 <= z < T.shape[2]
+        k = int(lab[y, x, z]) if inside else -1
+        if k < 0 or k >= len(g):
+            raise ValueError(f"getPathsToNearest: start {p} ({x}, {y}, {z}) belongs to no goal (label {k})")
+        ends[p] = g[k]
+    res = _ctx().path3d_batch(T, inits, ends, float(tau))
+    bad = [p for p, (_, status) in enumerate(res) if status == PATH_ERROR]
+    if bad:
+        raise IndexError(f"getPathsToNearest: the descent of path {bad[0]} left the volume (getPathGDM raises here too)")
     return [path for path, _ in res]

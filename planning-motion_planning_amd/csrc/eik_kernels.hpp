@@ -229,6 +229,28 @@ hipError_t fim3d_persist_init(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, 
                               hipStream_t st);
 hipError_t fim3d_persist(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, int grid, hipStream_t st);
 int fim3d_persist_resident(bool f64, int cus);
+// Seed sets on the 3D solver (fim3d.hip): one volume, K <= kMaxSeeds seeds.
+struct Seed3Desc {
+    int64_t x, y, z;  // inside the volume
+    double t0;        // finite, >= 0 (never -0), already rounded to the solve's dtype
+};
+// fim3d_init / fim3d_persist_init with no goal, then T[seed] = min(T, t0) and the seeds' tiles (and the
+// neighbours across the faces they lie on) listed / queued
+hipError_t fim3d_init_seeds(const Fim3dArgs& a, bool f64, const Seed3Desc* d_seeds, int64_t K, hipStream_t st);
+hipError_t fim3d_persist_init_seeds(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, const Seed3Desc* d_seeds,
+                                    int64_t K, hipStream_t st);
+struct Label3Args {
+    const void* T;           // [H][W][L] converged field (R), device
+    int64_t H, W, L, n;      // n = H * W * L < 2^31
+    const Seed3Desc* seeds;  // [K], device: the seeds that produced T
+    int K;
+    int* par;                // [n] scratch: parent, then the chain's end
+    int* label;              // [n] out
+    unsigned* flags;         // [kLabelPasses] scratch: pass p moved a pointer
+};
+// label[c] by the rule of include/eikonal.h (eik_labels3d_dev), asynchronous on st, no read-back (seeds.hip)
+hipError_t labels3d(const Label3Args& l, bool f64, hipStream_t st);
+int labels3d_passes(int64_t n);  // the jump passes it launches: ceil(log2(n))
 // FastMarching3D.computeTmap's early exit at `start` (:141) from a converged field Tf into Te
 // (a separate buffer); ts_off = start's linear index, or -1 for no early exit (fim3d.hip).
 hipError_t fim3d_early(const void* cost, const void* Tf, void* Te, int64_t H, int64_t W, int64_t L, int64_t ts_off,

@@ -152,6 +152,7 @@ struct Stage {
 
 using SeedStage = Stage<SeedDesc>;
 using RootStage = Stage<RootDesc>;
+using Seed3Stage = Stage<Seed3Desc>;
 
 }  // namespace
 
@@ -239,6 +240,7 @@ struct eik_ctx {
     double diff_share = -1.0;          // EIK_OPT_DIFF_SHARE (< 0: kDiffFullShare)
     SeedStage lab_seeds;               // eik_labels2d_dev: its seeds, and its scratch (parents | pass flags)
     DevBuf lab_work, lab_out;          // (lab_out: the host entries' device labels)
+    Seed3Stage seeds3, lab_seeds3;     // eik_fim3d_solve_seeds / eik_labels3d_dev: their seeds (scratch: lab_work)
     std::vector<DescBlock> desc;       // batched paths: descriptor blocks in flight or free (stage_desc)
     size_t desc_next = 0;
 };
@@ -489,6 +491,10 @@ void eik_destroy(eik_ctx* c) {
         if (e) (void)hipEventDestroy(e);
     if (c->lab_seeds.ev) (void)hipEventSynchronize(c->lab_seeds.ev);
     c->lab_seeds.release();
+    for (Seed3Stage* s : {&c->seeds3, &c->lab_seeds3}) {
+        if (s->ev) (void)hipEventSynchronize(s->ev);
+        s->release();
+    }
     c->pool = nullptr;  // (the process-wide pool stays)
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
@@ -2996,7 +3002,9 @@ static int layered_plan(eik_ctx* c, const void* d_cost, int64_t H, int64_t W, in
 // all B volumes share one device FIFO (fim_engine.hpp), a visit's face activations queue the
 // neighbours into the running launch -- no per-iteration launches or host syncs (the list driver
 // took 16-32 launches of ~41 us on the planner's 60 x 60 x 41 end-effector volume).
-static int fim3d_solve_persist(eik_ctx* c, Fim3dArgs a, int64_t B, int dtype, const int64_t* goals, hipStream_t st) {
+// d_seeds (B = 1): a seed set in place of the goals (fim3d_persist_init_seeds)
+static int fim3d_solve_persist(eik_ctx* c, Fim3dArgs a, int64_t B, int dtype, const int64_t* goals, hipStream_t st,
+                               const Seed3Desc* d_seeds = nullptr, int64_t K = 0) {
     const int64_t tiles = a.capacity;
     uint64_t nq = 4096;
     while (nq < 8 * (uint64_t)tiles) nq <<= 1;
@@ -3029,9 +3037,13 @@ static int fim3d_solve_persist(eik_ctx* c, Fim3dArgs a, int64_t B, int dtype, co
     hipEvent_t e0 = c->e3[0], e1 = c->e3[1];
     HIPCHK(c, hipEventRecord(e0, st));
     HIPCHK(c, hipMemsetAsync(c->q3vis.p, 0, 3 * sizeof(unsigned long long), st));
-    HIPCHK(c, c->goals.ensure(sizeof(int64_t) * 3 * B));
-    HIPCHK(c, hipMemcpyAsync(c->goals.p, goals, sizeof(int64_t) * 3 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, fim3d_persist_init(a, q, f64, (const int64_t*)c->goals.p, (int)B, st));
+    if (d_seeds) {
+        HIPCHK(c, fim3d_persist_init_seeds(a, q, f64, d_seeds, K, st));
+    } else {
+        HIPCHK(c, c->goals.ensure(sizeof(int64_t) * 3 * B));
+        HIPCHK(c, hipMemcpyAsync(c->goals.p, goals, sizeof(int64_t) * 3 * B, hipMemcpyHostToDevice, st));
+        HIPCHK(c, fim3d_persist_init(a, q, f64, (const int64_t*)c->goals.p, (int)B, st));
+    }
     HIPCHK(c, fim3d_persist(a, q, f64, grid, st));
     HIPCHK(c, hipEventRecord(e1, st));
     unsigned* hq = c->h_q3;
@@ -3061,8 +3073,10 @@ static int fim3d_solve_persist(eik_ctx* c, Fim3dArgs a, int64_t B, int dtype, co
 // goals: B x (x, y, z), host memory.
 // stop_off >= 0 (B = 1): FastMarching3D.computeTmap's early exit at that cell follows, so cells are
 // only lowered to values the early-exit field keeps (Fim3dArgs::stop_off)
+// d_seeds (B = 1, goals unused): the volume is seeded from the K device descriptors instead of a goal
 static int fim3d_solve_batch(eik_ctx* c, const void* d_cost, void* d_T, int64_t B, int64_t H, int64_t W, int64_t L,
-                             int dtype, const int64_t* goals, hipStream_t st, int64_t stop_off = -1) {
+                             int dtype, const int64_t* goals, hipStream_t st, int64_t stop_off = -1,
+                             const Seed3Desc* d_seeds = nullptr, int64_t K = 0) {
     Fim3dArgs a{};
     a.cost = d_cost;
     a.T = d_T;
@@ -3087,7 +3101,7 @@ static int fim3d_solve_batch(eik_ctx* c, const void* d_cost, void* d_T, int64_t 
     a.capacity = (int)tiles;
     a.max_passes = c->passes > 0 ? c->passes : c->max_passes3;
     if (c->mode == kModePersistent && H * W * L * (dtype == EIK_F64 ? 8 : 4) < (int64_t)UINT32_MAX)
-        return fim3d_solve_persist(c, a, B, dtype, goals, st);
+        return fim3d_solve_persist(c, a, B, dtype, goals, st, d_seeds, K);
     HIPCHK(c, c->l3.ensure(sizeof(int) * 3 * tiles));
     HIPCHK(c, c->c3.ensure(sizeof(int) * 64));
     HIPCHK(c, c->m3.ensure(sizeof(unsigned) * tiles));
@@ -3104,9 +3118,13 @@ static int fim3d_solve_batch(eik_ctx* c, const void* d_cost, void* d_T, int64_t 
     hipEvent_t e0 = c->e3[0], e1 = c->e3[1];
     HIPCHK(c, hipEventRecord(e0, st));
     HIPCHK(c, hipMemsetAsync(c->v3.p, 0, sizeof(unsigned long long), st));
-    HIPCHK(c, c->goals.ensure(sizeof(int64_t) * 3 * B));
-    HIPCHK(c, hipMemcpyAsync(c->goals.p, goals, sizeof(int64_t) * 3 * B, hipMemcpyHostToDevice, st));
-    HIPCHK(c, fim3d_init(a, dtype == EIK_F64, (const int64_t*)c->goals.p, (int)B, st));
+    if (d_seeds) {
+        HIPCHK(c, fim3d_init_seeds(a, dtype == EIK_F64, d_seeds, K, st));
+    } else {
+        HIPCHK(c, c->goals.ensure(sizeof(int64_t) * 3 * B));
+        HIPCHK(c, hipMemcpyAsync(c->goals.p, goals, sizeof(int64_t) * 3 * B, hipMemcpyHostToDevice, st));
+        HIPCHK(c, fim3d_init(a, dtype == EIK_F64, (const int64_t*)c->goals.p, (int)B, st));
+    }
     int* h = c->h3;
     const int grid = c->grid > 0 ? c->grid : 4 * c->cu_count;
     const int64_t max_iters = 64 * ((int64_t)a.ntx + a.nty + a.ntz) + 8 * tiles + 4096;
@@ -3175,6 +3193,84 @@ static int fim3d_solve_one(eik_ctx* c, const void* d_cost, void* d_T, int64_t H,
     return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, goal, st, stop_off);
 }
 
+// ---- goal sets for 3D solves (fim3d.hip seeding, seeds.hip labels3d)
+// The host checks shared by the seeded solve and the labels: on EIK_OK out holds the K descriptors, t0
+// rounded to the dtype.  Every failure is EIK_ERR_ARG with the offending index; nothing is launched.
+static int seeds3_check(eik_ctx* c, const char* who, int64_t H, int64_t W, int64_t L, int dtype, const int64_t* seeds,
+                        const double* t0, int64_t K, std::vector<Seed3Desc>& out) {
+    if (dtype != EIK_F32 && dtype != EIK_F64) return set_err(c, EIK_ERR_ARG, "%s: bad dtype %d", who, dtype);
+    if (H < 1 || W < 1 || L < 1)
+        return set_err(c, EIK_ERR_ARG, "%s: bad shape %ld x %ld x %ld", who, (long)H, (long)W, (long)L);
+    if (K < 1 || K > kMaxSeeds) return set_err(c, EIK_ERR_ARG, "%s: K = %ld seeds (1 .. 2^24)", who, (long)K);
+    if (!seeds) return set_err(c, EIK_ERR_ARG, "%s: seeds is NULL", who);
+    out.resize((size_t)K);
+    for (int64_t k = 0; k < K; ++k) {
+        const int64_t x = seeds[3 * k], y = seeds[3 * k + 1], z = seeds[3 * k + 2];
+        if (x < 0 || y < 0 || z < 0 || x >= W || y >= H || z >= L)
+            return set_err(c, EIK_ERR_ARG, "%s: seed %ld (%ld, %ld, %ld) outside %ldx%ldx%ld", who, (long)k, (long)x, (long)y,
+                           (long)z, (long)H, (long)W, (long)L);
+        double v = t0 ? t0[k] : 0.0;
+        if (!(v >= 0.0) || std::isinf(v))
+            return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g (finite and >= 0 needed)", who, (long)k, v);
+        if (dtype != EIK_F64) {
+            v = (double)(float)v;
+            if (std::isinf(v)) return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g rounds to +inf in fp32", who, (long)k, t0[k]);
+        }
+        out[k] = Seed3Desc{x, y, z, v + 0.0};  // (+ 0.0: -0 -> +0, values order like their bits)
+    }
+    return EIK_OK;
+}
+
+// Always the general solver (fim3d_solve_batch: the persistent driver under 4 GiB in persistent mode, else
+// the list driver), never layered_plan: the layered solver has no seeding of its own.
+int eik_fim3d_solve_seeds(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
+                          const int64_t* seeds, const double* t0, int64_t K, void* stream) {
+    if (!c) return EIK_ERR_ARG;
+    const char* who = "eik_fim3d_solve_seeds";
+    if (!d_cost || !d_T) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_cost ? "d_cost" : "d_T");
+    std::vector<Seed3Desc> v;
+    int rc = seeds3_check(c, who, H, W, L, dtype, seeds, t0, K, v);
+    if (rc) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    rc = seeds_upload(c, c->seeds3, v, st);
+    if (rc) return rc;
+    return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, nullptr, st, -1, c->seeds3.d, K);
+}
+
+// Nearest-goal labels of a converged volume (seeds.hip labels3d): asynchronous on `stream`, no read-back.
+int eik_labels3d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                     const double* t0, int64_t K, int32_t* d_label, void* stream) {
+    if (!c) return EIK_ERR_ARG;
+    const char* who = "eik_labels3d_dev";
+    if (!d_T || !d_label) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_T ? "d_T" : "d_label");
+    std::vector<Seed3Desc> v;
+    int rc = seeds3_check(c, who, H, W, L, dtype, seeds, t0, K, v);
+    if (rc) return rc;
+    // (each of H, W, L checked first: the product of three values below 2^31 / of any two cannot wrap)
+    if (H >= (1ll << 31) || W >= (1ll << 31) || L >= (1ll << 31) || H * W >= (1ll << 31) || H * W * L >= (1ll << 31))
+        return set_err(c, EIK_ERR_ARG, "%s: %ld x %ld x %ld cells (fewer than 2^31 needed)", who, (long)H, (long)W, (long)L);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = H * W * L;
+    HIPCHK(c, c->lab_work.ensure(sizeof(int) * (size_t)n + sizeof(unsigned) * kLabelPasses));
+    rc = seeds_upload(c, c->lab_seeds3, v, st);
+    if (rc) return rc;
+    Label3Args l{};
+    l.T = d_T;
+    l.H = H;
+    l.W = W;
+    l.L = L;
+    l.n = n;
+    l.seeds = c->lab_seeds3.d;
+    l.K = (int)K;
+    l.par = (int*)c->lab_work.p;
+    l.label = d_label;
+    l.flags = (unsigned*)(l.par + n);
+    HIPCHK(c, labels3d(l, dtype == EIK_F64, st));
+    return EIK_OK;
+}
+
 }  // extern "C"
 
 // Linear index of `start` for the early exit of FastMarching3D.computeTmap (:141), or -1 when the
@@ -3213,7 +3309,46 @@ static int tmap3d_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, int64_t 
     return EIK_OK;
 }
 
+// one volume from a seed set; labels (optional) from the field while it is on the device
+template <typename R>
+static int tmap3d_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                             const double* t0, int64_t K, R* T, int32_t* labels) {
+    if (!c) return EIK_ERR_ARG;
+    if (!cost || !T) return set_err(c, EIK_ERR_ARG, "eik_tmap3d_seeds: %s is NULL", !cost ? "cost" : "T");
+    constexpr int dtype = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
+    std::vector<Seed3Desc> v;  // (checked before anything is uploaded; the entry points below check again)
+    int rc = seeds3_check(c, "eik_tmap3d_seeds", H, W, L, dtype, seeds, t0, K, v);
+    if (rc) return rc;
+    if (labels && (H >= (1ll << 31) || W >= (1ll << 31) || L >= (1ll << 31) || H * W >= (1ll << 31) ||
+                   H * W * L >= (1ll << 31)))
+        return set_err(c, EIK_ERR_ARG, "eik_tmap3d_seeds: labels need fewer than 2^31 cells");
+    const int64_t n = H * W * L;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
+    HIPCHK(c, c->T.ensure(sizeof(R) * n));
+    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
+    rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = eik_fim3d_solve_seeds(c, c->cost.p, c->T.p, H, W, L, dtype, seeds, t0, K, c->stream);
+    if (!rc && labels) rc = eik_labels3d_dev(c, c->T.p, dtype, H, W, L, seeds, t0, K, (int32_t*)c->lab_out.p, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
+    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
 extern "C" {
+
+int eik_tmap3d_seeds_f32(eik_ctx* c, const float* cost, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                         const double* t0, int64_t K, float* T, int32_t* labels) {
+    return tmap3d_seeds_host<float>(c, cost, H, W, L, seeds, t0, K, T, labels);
+}
+
+int eik_tmap3d_seeds_f64(eik_ctx* c, const double* cost, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
+                         const double* t0, int64_t K, double* T, int32_t* labels) {
+    return tmap3d_seeds_host<double>(c, cost, H, W, L, seeds, t0, K, T, labels);
+}
 
 int eik_fim3d_early_exit(eik_ctx* c, const void* d_cost, const void* d_T, void* d_Te, int64_t H, int64_t W, int64_t L,
                          int dtype, const int64_t goal[3], const int64_t start[3], void* stream) {

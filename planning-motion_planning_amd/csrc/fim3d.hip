@@ -380,6 +380,85 @@ hipError_t fim3d_persist_init(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, 
     return hipGetLastError();
 }
 
+// ---- seed sets: one volume seeded from K cells, each with a start value t0 >= 0.
+// The sweep needs nothing new: process_tile3 keeps nv < v and treats no cell specially, so the field of
+// the set is the fixed point the unchanged kernels reach from "T = +inf, T[seed k] = min t0_k".
+// One thread per seed, after the init kernel (T = +inf, marks / queue state cleared, no goal).  t0 >= 0,
+// so values order like their bit patterns and the min is an unsigned atomic one: of two seeds on one cell
+// the lower holds, in any order of arrival.  The tiles are for_goal_tiles': a seed that nothing lowers is
+// handed across a face by its activation alone, exactly as the single goal is.
+template <typename R>
+__device__ __forceinline__ void seed_min3(const Fim3dArgs& a, const Seed3Desc& s) {
+    using U = typename Real<R>::U;
+    const R t0 = (R)s.t0;  // (the host checked: inside the volume, t0 finite and >= 0 in R, never -0)
+    U bits;
+    if constexpr (sizeof(R) == 8) bits = (U)__double_as_longlong(t0);
+    else bits = __float_as_uint(t0);
+    atomicMin(static_cast<U*>(a.T) + ((s.y * a.W + s.x) * a.L + s.z), bits);
+}
+
+// list driver: the seeds' tiles on list 0 (the marks, zeroed by the init kernel, keep a tile to one entry
+// however many seeds name it)
+template <typename R>
+__global__ __launch_bounds__(256) void fim3d_seeds_kernel(Fim3dArgs a, const Seed3Desc* __restrict__ seeds, int K) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const Seed3Desc s = seeds[k];
+    seed_min3<R>(a, s);
+    for_goal_tiles(a, 0, s.x, s.y, s.z, [&](int tile) { enqueue3(a, tile, 0, 1u); });
+}
+
+// persistent driver: the seeds' tiles queued (the state word keeps a tile to one FIFO entry: only the
+// push that finds it neither pending nor busy queues it, qpush_complete)
+template <typename R>
+__global__ __launch_bounds__(256) void fim3d_pseeds_kernel(Fim3dArgs a, Fim2dArgs q, const Seed3Desc* __restrict__ seeds,
+                                                           int K) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const Seed3Desc s = seeds[k];
+    seed_min3<R>(a, s);
+    __threadfence();
+    for_goal_tiles(a, 0, s.x, s.y, s.z, [&](int tile) { qpush(q, tile, kSelf); });
+}
+
+hipError_t fim3d_init_seeds(const Fim3dArgs& a, bool f64, const Seed3Desc* d_seeds, int64_t K, hipStream_t st) {
+    const int64_t n = a.H * a.W * a.L;
+    const int grid = (int)std::min<int64_t>(4096, (n + 255) / 256);
+    const int sg = (int)((K + 255) / 256);
+    const hipError_t e = hipMemsetAsync(a.counts, 0, 3 * sizeof(int), st);
+    if (e != hipSuccess) return e;
+    if (f64) {
+        hipLaunchKernelGGL(fim3d_init_kernel<double>, dim3(grid), dim3(256), 0, st, static_cast<double*>(a.T), n,
+                           a.mark, (int64_t)a.capacity);
+        hipLaunchKernelGGL(fim3d_seeds_kernel<double>, dim3(sg), dim3(256), 0, st, a, d_seeds, (int)K);
+    } else {
+        hipLaunchKernelGGL(fim3d_init_kernel<float>, dim3(grid), dim3(256), 0, st, static_cast<float*>(a.T), n,
+                           a.mark, (int64_t)a.capacity);
+        hipLaunchKernelGGL(fim3d_seeds_kernel<float>, dim3(sg), dim3(256), 0, st, a, d_seeds, (int)K);
+    }
+    return hipGetLastError();
+}
+
+hipError_t fim3d_persist_init_seeds(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, const Seed3Desc* d_seeds,
+                                    int64_t K, hipStream_t st) {
+    const int64_t n = a.H * a.W * a.L;
+    const int64_t nslots = (int64_t)q.qmask + 1;
+    const int grid = (int)std::min<int64_t>(4096, (std::max<int64_t>(n, nslots) + 255) / 256);
+    const hipError_t e = hipMemsetAsync(q.qhead, 0, kQueueCtlBytes, st);  // head tail active error
+    if (e != hipSuccess) return e;
+    const int sg = (int)((K + 255) / 256);
+    if (f64) {
+        hipLaunchKernelGGL(fim3d_pinit_kernel<double>, dim3(grid), dim3(256), 0, st, static_cast<double*>(a.T), n,
+                           q.qstate, (int64_t)a.capacity, q.qslot, nslots);
+        hipLaunchKernelGGL(fim3d_pseeds_kernel<double>, dim3(sg), dim3(256), 0, st, a, q, d_seeds, (int)K);
+    } else {
+        hipLaunchKernelGGL(fim3d_pinit_kernel<float>, dim3(grid), dim3(256), 0, st, static_cast<float*>(a.T), n,
+                           q.qstate, (int64_t)a.capacity, q.qslot, nslots);
+        hipLaunchKernelGGL(fim3d_pseeds_kernel<float>, dim3(sg), dim3(256), 0, st, a, q, d_seeds, (int)K);
+    }
+    return hipGetLastError();
+}
+
 hipError_t fim3d_persist(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, int grid, hipStream_t st) {
     if (f64)
         hipLaunchKernelGGL(fim3d_persist_kernel<double>, dim3(grid), dim3(256), 0, st, a, q);

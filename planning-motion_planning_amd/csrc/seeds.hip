@@ -15,6 +15,8 @@
 //   labels               label[c] = the seed whose wave reached c first, by the rule of include/eikonal.h:
 //                        parents (the lowest strictly lower 4-neighbour), roots (seeds that hold their
 //                        own T0), pointer jumping to the roots, a gather of the roots' labels.
+//   labels3d             the same rule on a volume with 6 neighbours (§3.16; its seeding is fim3d.hip's):
+//                        parent and root kernels of its own, the jumping and the gather shared.
 #include "fim_engine.hpp"
 
 namespace eik {
@@ -142,7 +144,87 @@ __global__ __launch_bounds__(256) void labels_gather_kernel(LabelArgs l) {
     }
 }
 
+// ------------------------------------------------------------------------------- labels, 3D
+// The same rule on one [H][W][L] volume (z fastest) with 6 neighbours.  Only the parents
+// and the roots know the dimension: pointer jumping and the gather above work on cell indices.
+// Cell i: its parent (itself: no parent) and label -1.
+template <typename R>
+__global__ __launch_bounds__(256) void labels3d_parent_kernel(Label3Args l) {
+    const R* const T = static_cast<const R*>(l.T);
+    const int64_t wl = l.W * l.L;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < l.n; i += stride) {
+        const int64_t z = i % l.L, xy = i / l.L, x = xy % l.W, y = xy / l.W;
+        const R t = T[i];
+        R best = t;
+        int64_t p = i;
+        if (t < Real<R>::inf()) {
+            // the smallest neighbour strictly below t; of equal ones the first of x-1, x+1, y-1, y+1, z-1,
+            // z+1 (the order of fim3d.hip's faces)
+            auto nb = [&](bool in, int64_t j) {
+                if (!in) return;
+                const R v = T[j];
+                if (v < best) {
+                    best = v;
+                    p = j;
+                }
+            };
+            nb(x > 0, i - l.L);
+            nb(x + 1 < l.W, i + l.L);
+            nb(y > 0, i - wl);
+            nb(y + 1 < l.H, i + wl);
+            nb(z > 0, i - 1);
+            nb(z + 1 < l.L, i + 1);
+        }
+        l.par[i] = (int)p;
+        l.label[i] = -1;
+    }
+}
+
+// Seed k is a root when T at its cell is its T0 bit for bit (labels_root_kernel's rule)
+template <typename R>
+__global__ __launch_bounds__(256) void labels3d_root_kernel(Label3Args l) {
+    using U = typename SeedBits<R>::U;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= l.K) return;
+    const Seed3Desc s = l.seeds[k];
+    const int64_t i = (s.y * l.W + s.x) * l.L + s.z;
+    if (static_cast<const U*>(l.T)[i] != SeedBits<R>::of((R)s.t0)) return;  // undercut by another seed's wave
+    l.par[i] = (int)i;
+    atomicMin(reinterpret_cast<unsigned*>(l.label) + i, (unsigned)k);
+}
+
 // ------------------------------------------------------------------------- host launchers
+int labels3d_passes(int64_t n) {
+    int p = 1;
+    while (p < kLabelPasses && (1ll << p) < n) ++p;
+    return p;
+}
+
+hipError_t labels3d(const Label3Args& l, bool f64, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(l.flags, 0, sizeof(unsigned) * kLabelPasses, st);
+    if (e != hipSuccess) return e;
+    const int grid = (int)std::min<int64_t>(8192, (l.n + 255) / 256);
+    const int kgrid = (l.K + 255) / 256;
+    if (f64) {
+        hipLaunchKernelGGL(labels3d_parent_kernel<double>, dim3(grid), dim3(256), 0, st, l);
+        hipLaunchKernelGGL(labels3d_root_kernel<double>, dim3(kgrid), dim3(256), 0, st, l);
+    } else {
+        hipLaunchKernelGGL(labels3d_parent_kernel<float>, dim3(grid), dim3(256), 0, st, l);
+        hipLaunchKernelGGL(labels3d_root_kernel<float>, dim3(kgrid), dim3(256), 0, st, l);
+    }
+    // the dimension-free half: the jump and gather kernels read par, label, flags and n only
+    LabelArgs j{};
+    j.n = l.n;
+    j.par = l.par;
+    j.label = l.label;
+    j.flags = l.flags;
+    const int passes = labels3d_passes(l.n);
+    for (int p = 0; p < passes; ++p) hipLaunchKernelGGL(labels_jump_kernel, dim3(grid), dim3(256), 0, st, j, p);
+    hipLaunchKernelGGL(labels_gather_kernel, dim3(grid), dim3(256), 0, st, j);
+    return hipGetLastError();
+}
+
 hipError_t fim2d_start_seeds(const Fim2dArgs& a, bool f64, const SeedDesc* d_seeds, int64_t K, hipStream_t st) {
     const int grid = (int)((K + 255) / 256);
     if (f64)

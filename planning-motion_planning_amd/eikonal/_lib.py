@@ -238,6 +238,11 @@ def lib():
         L.eik_fim2d_diff_info.argtypes = [vp, _i64p]
         L.eik_tmap2d_update_cost_f32.argtypes = [vp, _f32p, _f32p, _f32p, i64, i64, i64, i64]
         L.eik_tmap2d_update_cost_f64.argtypes = [vp, _f64p, _f64p, _f64p, i64, i64, i64, i64]
+        # goal sets for 3D solves: t0 / labels are nullable host arrays (passed as an address or None)
+        L.eik_fim3d_solve_seeds.argtypes = [vp, vp, vp, i64, i64, i64, C.c_int, _i64p, vp, i64, vp]
+        L.eik_labels3d_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, _i64p, vp, i64, vp, vp]
+        L.eik_tmap3d_seeds_f32.argtypes = [vp, _f32p, i64, i64, i64, _i64p, vp, i64, _f32p, vp]
+        L.eik_tmap3d_seeds_f64.argtypes = [vp, _f64p, i64, i64, i64, _i64p, vp, i64, _f64p, vp]
         _lib = L
         return L
 
@@ -274,6 +279,21 @@ def _seeds(seeds, t0, map_of=None):
     return s, t, m, K
 
 
+def _seeds3(seeds, t0):
+    """(seeds int64 [K][3], t0 float64 [K] or None, K) as host arrays for the 3D goal-set entry points"""
+    s = np.asarray(seeds)
+    if s.ndim != 2 or s.shape[1] != 3:
+        raise ValueError(f"seeds must be K nodes (x, y, z), not shape {s.shape}")
+    s = np.ascontiguousarray(s, dtype=np.int64)
+    K = len(s)
+    t = None
+    if t0 is not None:
+        t = np.ascontiguousarray(t0, dtype=np.float64).reshape(-1)
+        if len(t) != K:
+            raise ValueError(f"{K} seeds but {len(t)} start values")
+    return s, t, K
+
+
 def _addr(a):
     return None if a is None else a.ctypes.data
 
@@ -303,6 +323,7 @@ EXPORTED = [
     "eik_tmap2d_update_seeds_f64",
     "eik_cost_diff_dev", "eik_fim2d_resolve_cost", "eik_fim2d_diff_info", "eik_tmap2d_update_cost_f32",
     "eik_tmap2d_update_cost_f64",
+    "eik_fim3d_solve_seeds", "eik_labels3d_dev", "eik_tmap3d_seeds_f32", "eik_tmap3d_seeds_f64",
 ]
 
 
@@ -606,6 +627,52 @@ class Context:
             fn = lib().eik_tmap3d_early_f64 if f64 else lib().eik_tmap3d_early_f32
             self._chk(fn(self._h, cost, H, W, Lz, g, s, T))
         return T
+
+    # -- goal sets for 3D solves (eik_fim3d_solve_seeds, eik_labels3d_dev, eik_tmap3d_seeds_*): one
+    # volume on the general 3D solver, seeds K x (x, y, z), t0 their start values (None: all 0)
+    def tmap3d_seeds(self, cost, seeds, t0=None, dtype=np.float64, labels=False):
+        """The field of a seed set in a volume cost[y, x, z] -> T, or (T, labels int32: the seed each cell
+        belongs to, -1 = none) with labels=True."""
+        cost = np.ascontiguousarray(cost, dtype=dtype)
+        if cost.ndim != 3:
+            raise ValueError(f"tmap3d_seeds: cost must be a volume H x W x L, not shape {cost.shape}")
+        H, W, Lz = cost.shape
+        s, t, K = _seeds3(seeds, t0)
+        T = result_empty(cost.shape, cost.dtype)
+        lab = np.empty(cost.shape, np.int32) if labels else None
+        fn = lib().eik_tmap3d_seeds_f64 if cost.dtype == np.float64 else lib().eik_tmap3d_seeds_f32
+        self._chk(fn(self._h, cost, H, W, Lz, s, _addr(t), K, T, _addr(lab)))
+        return (T, lab) if labels else T
+
+    def fim3d_solve_seeds(self, d_cost, d_T, H, W, L, dtype, seeds, t0=None, stream=None):
+        """eik_fim3d_solve_seeds on device buffers (addresses) of H x W x L cells in dtype (EIK_F32 /
+        EIK_F64); synchronous, stats() afterwards as after any 3D solve."""
+        s, t, K = _seeds3(seeds, t0)
+        self._chk(lib().eik_fim3d_solve_seeds(self._h, d_cost, d_T, H, W, L, dtype, s, _addr(t), K, stream))
+
+    def labels3d(self, T, seeds, t0=None):
+        """Nearest-goal labels (eik_labels3d_dev) of a converged volume T (H x W x L, float32 or float64, a
+        numpy array -- uploaded through torch -- or a torch tensor on this context's device) for the seed
+        list that produced it -> int32 labels of T's shape, of T's kind."""
+        import torch
+
+        host = not isinstance(T, torch.Tensor)
+        if host:
+            T = np.asarray(T)
+            T = np.ascontiguousarray(T, dtype=np.float32 if T.dtype == np.float32 else np.float64)
+            Td = torch.from_numpy(T).to(torch.device("cuda", self.device))
+        else:
+            Td = T.contiguous()
+        if Td.dtype not in (torch.float32, torch.float64) or Td.dim() != 3:
+            raise ValueError("labels3d: T must be a float32 / float64 volume H x W x L")
+        H, W, Lz = Td.shape
+        s, t, K = _seeds3(seeds, t0)
+        lab = torch.empty(Td.shape, dtype=torch.int32, device=Td.device)
+        stream = torch.cuda.current_stream(Td.device).cuda_stream
+        self._chk(lib().eik_labels3d_dev(self._h, Td.data_ptr(), EIK_F64 if Td.dtype == torch.float64 else EIK_F32,
+                                         H, W, Lz, s, _addr(t), K, lab.data_ptr(), stream))
+        torch.cuda.current_stream(Td.device).synchronize()
+        return lab.cpu().numpy() if host else lab
 
     def path3d(self, T, init, end, tau=0.5):
         T = np.ascontiguousarray(T, dtype=np.float64)
