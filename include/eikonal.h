@@ -158,9 +158,13 @@ typedef enum {
                                 _PRIO_DISPATCH); fp64 solves ignore it.                          */
     EIK_OPT_DIFF_LOADS = 21, /* the cost diff's loads (eik_cost_diff_dev, eik_fim2d_resolve_cost): 1
                                 (default) non-temporal, 0 plain; same results (tools/cost_diff_ab.py) */
-    EIK_OPT_DIFF_SHARE = 22  /* eik_fim2d_resolve_cost solves from scratch when more than this share
+    EIK_OPT_DIFF_SHARE = 22, /* eik_fim2d_resolve_cost solves from scratch when more than this share
                                 of the raster's tiles changed; < 0 (default): the measured constant
                                 (DESIGN.md §3.15); >= 1: never                                      */
+    EIK_OPT_SEEDS_LAYERED = 23 /* eik_fim3d_solve_seeds / eik_tmap3d_seeds_*: 0 (default) = always the
+                                general 3D solver; 1 = few-layer volumes go to the layered solver by
+                                eik_fim3d_solve's own rule when every seed's z lies among the solved
+                                layers (eik_fim3d_last_solver tells which ran)     */
 } eik_option;
 
 typedef enum { EIK_MODE_LIST = 0, EIK_MODE_PERSISTENT = 1 } eik_mode;
@@ -377,8 +381,8 @@ int eik_tmap2d_update_f64(eik_ctx* ctx, const double* cost_new, double* T_inout,
  * eik_fim2d_solve / eik_fim2d_adopt (any single-goal host solve on the context) binds a single-goal
  * solve again.
  * Not covered: the layered solver, the bidirectional fronts, a seeded eik_plan2d_batch.  3D volumes:
- * eik_fim3d_solve_seeds below (one volume on the general 3D solver; no 3D replanning, no B > 1, no
- * early exit with a seed set). */
+ * eik_fim3d_solve_seeds below (one volume on the general 3D solver or, with EIK_OPT_SEEDS_LAYERED, on the
+ * layered one; no 3D replanning, no B > 1, no early exit with a seed set). */
 int eik_fim2d_start_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
                           const int32_t* map_of, int64_t K, void* stream);
 int eik_fim2d_solve_seeds(eik_fim2d* fim, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
@@ -686,11 +690,24 @@ int eik_fim3d_solve(eik_ctx* ctx, const void* d_cost, void* d_T, int64_t H, int6
  * seeds: K x (x, y, z), host.  t0: K host doubles, rounded to dtype, or NULL (all 0).  The host arrays
  * are read before the call returns and go to the device in stream order through a pinned block.
  *
- * eik_fim3d_solve_seeds  synchronous, like eik_fim3d_solve.  It always runs on the general 3D solver --
- *                        the persistent driver while the volume is under 4 GiB and the context is in
- *                        persistent mode, else the list driver -- also for the few-layer volumes that
- *                        eik_fim3d_solve gives to the layered solver.  eik_get_stats, EIK_OPT_PASSES,
- *                        EIK_OPT_GRID, EIK_OPT_QTIMEOUT and EIK_OPT_MAX_VISITS behave as in eik_fim3d_solve.
+ * eik_fim3d_solve_seeds  synchronous, like eik_fim3d_solve.  By default it always runs on the general 3D
+ *                        solver -- the persistent driver while the volume is under 4 GiB and the context
+ *                        is in persistent mode, else the list driver -- also for the few-layer volumes
+ *                        that eik_fim3d_solve gives to the layered solver.  With EIK_OPT_SEEDS_LAYERED = 1
+ *                        it routes as eik_fim3d_solve does for one goal: the layered solver takes the
+ *                        volume when the context is in persistent mode, EIK_OPT_MAX_ROUNDS is 1, a tile
+ *                        row band of the volume is under 4 GiB, the volume has at most 4 (fp32) / 3
+ *                        (fp64) layers -- or two more, the first and last all +inf -- and every seed's z
+ *                        lies among the solved layers; otherwise the general solver runs as before (a
+ *                        seed in a padding layer feeds its z neighbour, and the layered solver never
+ *                        reads the padding).  The field obeys the same bounds on either solver.
+ *                        eik_get_stats, EIK_OPT_PASSES, EIK_OPT_GRID, EIK_OPT_QTIMEOUT and
+ *                        EIK_OPT_MAX_VISITS behave as in eik_fim3d_solve (on the layered solver also
+ *                        EIK_OPT_PRIO, with the seeds' t0 as keys, and EIK_OPT_LAYER_PLANAR).
+ * eik_fim3d_last_solver  what the last 3D solve on the context (eik_fim3d_solve, eik_fim3d_solve_seeds and
+ *                        the host entries above them) ran on: out[0] = 1 the layered solver, 0 the
+ *                        general one; out[1] = z0, the first solved layer; out[2] = nl, the solved layers
+ *                        (0 on the general solver); out[3] = 1 when priority bands were set up.
  * eik_labels3d_dev       the labels of a converged field d_T of H x W x L cells in dtype (fewer than 2^31
  *                        cells) for the seed list that produced it -> d_label, int32 [H][W][L], device.
  *                        Asynchronous on `stream`, no read-back.  The context owns the scratch (shared
@@ -709,9 +726,11 @@ int eik_fim3d_solve(eik_ctx* ctx, const void* d_cost, void* d_T, int64_t H, int6
  * EIK_ERR_ARG, with a message naming the offending index and nothing launched: K < 1 or K > 2^24, a
  * NULL pointer, a seed outside the volume, a t0 that is negative, NaN or +inf or (fp32) rounds to +inf,
  * H, W or L < 1.
- * Not covered: 3D replanning, B > 1 volumes per call, the layered solver, early exit with a seed set. */
+ * Not covered: seeds on decomposition blocks (eik_fim3dl_* handles), 3D replanning, B > 1 volumes per
+ * call, early exit with a seed set. */
 int eik_fim3d_solve_seeds(eik_ctx* ctx, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
                           const int64_t* seeds, const double* t0, int64_t K, void* stream);
+int eik_fim3d_last_solver(const eik_ctx* ctx, int64_t out[4]);
 int eik_labels3d_dev(eik_ctx* ctx, const void* d_T, int dtype, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
                      const double* t0, int64_t K, int32_t* d_label, void* stream);
 

@@ -26,7 +26,7 @@ import numpy as np
 from numpy import array
 
 from eikonal import default_context, PATH_ERROR
-from eikonal._lib import OPT_EXACT_BAND
+from eikonal._lib import OPT_EXACT_BAND, OPT_SEEDS_LAYERED
 
 _DTYPE = np.float32 if os.environ.get("EIKONAL_DTYPE", "float64") in ("float32", "f32") else np.float64
 
@@ -176,19 +176,31 @@ def _goal_list(goals, shape):
     return np.ascontiguousarray(g[:, :3], dtype=np.int64)
 
 
-def computeTmapMulti(costMap, goals, offsets=None, labels=False):
+def computeTmapMulti(costMap, goals, offsets=None, labels=False, layered=None):
     """No reference counterpart: the arrival-time field of a goal SET in a volume, min over the goals of
     (offset + cost-to-go), solved as one problem on the general 3D solver.  goals: K
     nodes (x, y, z), or a boolean mask of costMap's shape (its True cells, row-major); offsets: K start
     values >= 0 (None: all 0).  Returns the full field T (float64), or with labels=True (T, labels):
-    int32, the index into goals of the goal each cell belongs to, -1 for unreached cells."""
+    int32, the index into goals of the goal each cell belongs to, -1 for unreached cells.
+    layered: True lets a few-layer volume (the rover's (x, y, mode) cost maps) run on the layered solver
+    where computeTmap's own routing rule and the goals' layers allow (OPT_SEEDS_LAYERED),
+    False never; None (default) reads EIKONAL_SEEDS_LAYERED on every call (unset, empty or "0": off).  The
+    option is set for this call only: the shared context's previous value is put back afterwards."""
     cost = np.ascontiguousarray(costMap, dtype=_DTYPE)
     if cost.ndim != 3:
         raise ValueError(f"computeTmapMulti: costMap must be a volume, not shape {cost.shape}")
     g = _goal_list(goals, cost.shape)
     if len(g) == 0:
         raise ValueError("computeTmapMulti: no goal")
-    res = _ctx().tmap3d_seeds(cost, g, offsets, dtype=_DTYPE, labels=labels)
+    if layered is None:
+        layered = os.environ.get("EIKONAL_SEEDS_LAYERED", "0") not in ("", "0")
+    c = _ctx()
+    before = c.get_option(OPT_SEEDS_LAYERED, 0.0)
+    c.set_option(OPT_SEEDS_LAYERED, 1 if layered else 0)
+    try:
+        res = c.tmap3d_seeds(cost, g, offsets, dtype=_DTYPE, labels=labels)
+    finally:
+        c.set_option(OPT_SEEDS_LAYERED, before)
     if labels:
         return res[0].astype(np.float64, copy=False), res[1]
     return res.astype(np.float64, copy=False)

@@ -239,6 +239,11 @@ struct Seed3Desc {
 hipError_t fim3d_init_seeds(const Fim3dArgs& a, bool f64, const Seed3Desc* d_seeds, int64_t K, hipStream_t st);
 hipError_t fim3d_persist_init_seeds(const Fim3dArgs& a, const Fim2dArgs& q, bool f64, const Seed3Desc* d_seeds,
                                     int64_t K, hipStream_t st);
+// ... and on the layered solver (fim2dl.hip): fim2dl_init with no goal, then T[seed] =
+// min(T, t0) and the seeds' tiles (and the neighbours across the sides they lie on) queued with key t0.
+// z0_abs: the volume's first solved layer; every seed's z lies in [z0_abs, z0_abs + nl).  n as fim2dl_init's.
+hipError_t fim2dl_init_seeds(const Fim2dArgs& a, bool f64, const Seed3Desc* d_seeds, int64_t K, int z0_abs, int64_t n,
+                             hipStream_t st);
 struct Label3Args {
     const void* T;           // [H][W][L] converged field (R), device
     int64_t H, W, L, n;      // n = H * W * L < 2^31

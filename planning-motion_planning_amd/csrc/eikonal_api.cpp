@@ -193,6 +193,8 @@ struct eik_ctx {
     // traffic per launch 9.06 -> 3.92 GB (fp32), 20.3 -> 8.6 GB (fp64), the time within noise
     // (the layered sweep is VALU-bound; profiles/r05c_pmc_traffic_c5*.json, r05h_prio_planar_ab.log)
     int layer_planar = 1;
+    int seeds_layered = 0;       // EIK_OPT_SEEDS_LAYERED: eik_fim3d_solve_seeds routes as eik_fim3d_solve does
+    int64_t last_solver3[4] = {};  // eik_fim3d_last_solver: layered solver ran, z0, nl, bands set up
     DevBuf lp_cost, lp_T;        // those copies (solve_layered)
     int path_loop = 4;           // EIK_OPT_PATH_LOOP: 2D walker loop form (4: lane pairs, round 5,
                                  // 0.405 -> 0.30 us/step on the bench path, profiles/r05k_walker_ab.log)
@@ -527,6 +529,7 @@ int eik_set_option(eik_ctx* c, int opt, double v) {
         case EIK_OPT_PRIO_RING: c->prio_ring = v < 0 ? 0 : (int)std::min(v, 1073741824.0); break;
         case EIK_OPT_PRIO_DISPATCH: c->prio_dispatch = v < 0 ? 0 : (int)std::min(v, 128.0); break;
         case EIK_OPT_LAYER_PLANAR: c->layer_planar = v != 0; break;
+        case EIK_OPT_SEEDS_LAYERED: c->seeds_layered = v != 0; break;
         case EIK_OPT_PATH_LOOP: c->path_loop = std::max(0, std::min(4, (int)v)); break;
         case EIK_OPT_EXACT_BAND: c->exact_band = v != 0; break;
         case EIK_OPT_WIDE: c->wide = v < 0 ? -1 : v != 0 ? 1 : 0; break;
@@ -2868,8 +2871,11 @@ int eik_plan2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, in
 // ------------------------------------------------------------------------------ 3D
 // Few-layer fp32 volumes (the rover's (x, y, mode) costmaps) on the layered 2D-tile solver:
 // layers z0 .. z0+nl-1 of a [H][W][L] volume, one persistent launch.
+// d_seeds: a seed set in place of the goal (fim2dl_init_seeds; every seed's z in [z0, z0 + nl), goal unused).
+// The bands' keys are then the seeds' t0, and a retry on the FIFO seeds again from the same list.
 static int solve_layered(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int z0, int nl,
-                         const int64_t goal[3], int dtype, hipStream_t st) {
+                         const int64_t goal[3], int dtype, hipStream_t st, const Seed3Desc* d_seeds = nullptr,
+                         int64_t K = 0) {
     const bool f64 = dtype == EIK_F64;
     const int th = fim2dl_rows(f64);
     eik_fim2d*& slot = f64 ? c->cached_l64 : c->cached_l;
@@ -2933,7 +2939,11 @@ static int solve_layered(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, i
         // 3.58, fp32 6.30-6.33 / 6.37-6.38 / 6.27 / 6.08-6.12 Gcells/s, profiles/r05ak_layered_dispatch_ab.log)
         a.disp = c->prio_dispatch > 0 ? (unsigned)c->prio_dispatch : a.tiles_per_map >= kWideTiles ? 64u : 32u;
     }
-    HIPCHK(c, fim2dl_init(a, f64, goal[0], goal[1], goal[2] - z0, nT, st));
+    if (d_seeds) {
+        HIPCHK(c, fim2dl_init_seeds(a, f64, d_seeds, K, z0, nT, st));
+    } else {
+        HIPCHK(c, fim2dl_init(a, f64, goal[0], goal[1], goal[2] - z0, nT, st));
+    }
     HIPCHK(c, fim2dl_persist(a, nl, f64, grid, st));
     if (planar) HIPCHK(c, layer_planar(c->lp_T.p, d_T, f64, H * W, L, z0, nl, false, st));
     HIPCHK(c, hipEventRecord(f->ev_stop, st));
@@ -2943,6 +2953,10 @@ static int solve_layered(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, i
     err = f->h_q[192 / 4];
     if (!(err & 4u) || (err & 3u)) break;
     }
+    c->last_solver3[0] = 1;  // eik_fim3d_last_solver
+    c->last_solver3[1] = z0;
+    c->last_solver3[2] = nl;
+    c->last_solver3[3] = a.bctl != nullptr;  // (of the attempt that stands)
     if (err & 1u)
         return set_err(c, EIK_ERR_HIP, "layered solver: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", c->qtimeout_s);
     if (err & 2u)
@@ -3084,6 +3098,7 @@ static int fim3d_solve_batch(eik_ctx* c, const void* d_cost, void* d_T, int64_t 
     a.W = W;
     a.L = L;
     a.stop_off = -1;
+    for (auto& v : c->last_solver3) v = 0;  // eik_fim3d_last_solver: the general solver
     if (stop_off >= 0 && B == 1) {
         HIPCHK(c, c->misc.ensure(64));
         HIPCHK(c, max_finite(d_cost, H * W * L, dtype == EIK_F64, (char*)c->misc.p + 32, st));
@@ -3221,8 +3236,11 @@ static int seeds3_check(eik_ctx* c, const char* who, int64_t H, int64_t W, int64
     return EIK_OK;
 }
 
-// Always the general solver (fim3d_solve_batch: the persistent driver under 4 GiB in persistent mode, else
-// the list driver), never layered_plan: the layered solver has no seeding of its own.
+// By default the general solver (fim3d_solve_batch: the persistent driver under 4 GiB in persistent mode,
+// else the list driver).  With EIK_OPT_SEEDS_LAYERED the few-layer volumes that fim3d_solve_one gives to the
+// layered solver go there too, by the same rule, once every seed's z lies among the solved layers: a seed in
+// an all-+inf padding layer feeds its z neighbour in the specification, and the layered solver never reads
+// the padding.
 int eik_fim3d_solve_seeds(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
                           const int64_t* seeds, const double* t0, int64_t K, void* stream) {
     if (!c) return EIK_ERR_ARG;
@@ -3235,7 +3253,23 @@ int eik_fim3d_solve_seeds(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, 
     hipStream_t st = (hipStream_t)stream;
     rc = seeds_upload(c, c->seeds3, v, st);
     if (rc) return rc;
+    const int64_t esz = dtype == EIK_F64 ? 8 : 4;
+    if (c->seeds_layered && c->mode == kModePersistent && c->max_rounds == 1 &&
+        (fim2dl_rows(dtype == EIK_F64) + 2) * W * L * esz < (int64_t)UINT32_MAX) {
+        int z0 = 0, nl = 0;
+        rc = layered_plan(c, d_cost, H, W, L, dtype, st, &z0, &nl);
+        if (rc) return rc;
+        bool inside = nl > 0;
+        for (int64_t k = 0; inside && k < K; ++k) inside = v[k].z >= z0 && v[k].z < z0 + nl;
+        if (inside) return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, nullptr, dtype, st, c->seeds3.d, K);
+    }
     return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, nullptr, st, -1, c->seeds3.d, K);
+}
+
+int eik_fim3d_last_solver(const eik_ctx* c, int64_t out[4]) {
+    if (!c || !out) return EIK_ERR_ARG;
+    for (int i = 0; i < 4; ++i) out[i] = c->last_solver3[i];
+    return EIK_OK;
 }
 
 // Nearest-goal labels of a converged volume (seeds.hip labels3d): asynchronous on `stream`, no read-back.

@@ -682,6 +682,32 @@ __global__ void fim2dl_seed_kernel(Fim2dArgs a, int64_t gx, int64_t gy, int64_t 
     activate_goal_sides(a, tile, (int)(gy % th), (int)(gx % kTile), th);
 }
 
+// Seed sets (seeds.hip's fim2d_seeds_kernel in the layered addressing): after the init
+// kernel with no goal, one thread per seed lowers T to (R)t0 with an unsigned atomic min on the bit pattern
+// (t0 >= 0: values order like their bits, so of two seeds on one cell the lower holds in any order of
+// arrival) and activates the seed's tile -- and the neighbour across every tile side the seed lies on --
+// with key t0.  The index serves both layouts: the volume's [y][x][L] and the layer-planar copy [nl][H][W]
+// (a.ls, a.z0, a.lzs).  z0_abs: the volume's first solved layer (the host checked every seed's z against
+// [z0_abs, z0_abs + nl)).  kVisited: a tile without it skips its first T read (kFreshSkipL) and would lose
+// the seed.  No edge-column copy: the layered solver keeps none.
+template <typename R>
+__global__ __launch_bounds__(256) void fim2dl_seeds_kernel(Fim2dArgs a, const Seed3Desc* __restrict__ seeds, int K,
+                                                           int z0_abs, int th) {
+    using U = typename Real<R>::U;
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const Seed3Desc s = seeds[k];
+    const R t0 = (R)s.t0;  // (the host checked: inside the volume, t0 finite and >= 0 in R, never -0)
+    U bits;
+    if constexpr (sizeof(R) == 8) bits = (U)__double_as_longlong(t0);
+    else bits = __float_as_uint(t0);
+    atomicMin(static_cast<U*>(a.T) + ((s.y * a.W + s.x) * a.ls + a.z0 + (s.z - z0_abs) * a.lzs), bits);
+    const int tile = (int)(s.y / th) * a.ntx + (int)(s.x / kTile);
+    const float key = (float)t0;  // (a double past the float range: +inf, the last band)
+    qpush(a, tile, kSelf | kVisited, key);
+    activate_seed_sides(a, tile, (int)(s.y % th), (int)(s.x % kTile), th, key);
+}
+
 
 // flag |= 1 if layer z of the [HW][L] volume holds a finite cost
 template <typename R>
@@ -824,6 +850,22 @@ hipError_t fim2dl_init(const Fim2dArgs& a, bool f64, int64_t gx, int64_t gy, int
         if (gx >= 0)
             hipLaunchKernelGGL(fim2dl_seed_kernel<float>, dim3(1), dim3(1), 0, st, a, gx, gy, gz, kRowsOf<float>);
     }
+    return hipGetLastError();
+}
+
+// A seed set in place of the goal: fim2dl_init's clear with no goal (T = +inf, queue state and slots), then
+// the K seeds in stream order (z0_abs: the volume's first solved layer; the seeds' z are the volume's)
+hipError_t fim2dl_init_seeds(const Fim2dArgs& a, bool f64, const Seed3Desc* d_seeds, int64_t K, int z0_abs, int64_t n,
+                             hipStream_t st) {
+    const hipError_t e = fim2dl_init(a, f64, -1, 0, 0, n, st);
+    if (e != hipSuccess) return e;
+    const int grid = (int)((K + 255) / 256);
+    if (f64)
+        hipLaunchKernelGGL(fim2dl_seeds_kernel<double>, dim3(grid), dim3(256), 0, st, a, d_seeds, (int)K, z0_abs,
+                           kRowsOf<double>);
+    else
+        hipLaunchKernelGGL(fim2dl_seeds_kernel<float>, dim3(grid), dim3(256), 0, st, a, d_seeds, (int)K, z0_abs,
+                           kRowsOf<float>);
     return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@ OPT_MAX_ROUNDS, OPT_SYNC_EVERY, OPT_TIMING, OPT_GRID, OPT_TOL, OPT_DELTA = 0, 1,
 OPT_MODE, OPT_QTIMEOUT, OPT_MAX_VISITS, OPT_PASSES, OPT_FRESH_FIRST, OPT_SCHED, OPT_PATH_LOOP = 6, 7, 8, 9, 10, 11, 12
 OPT_FRONTS_CAP, OPT_LIVE_PACK, OPT_PRIO, OPT_LAYER_PLANAR, OPT_PRIO_RING, OPT_PRIO_DISPATCH = 13, 14, 15, 16, 17, 18
 OPT_EXACT_BAND, OPT_WIDE, OPT_DIFF_LOADS, OPT_DIFF_SHARE = 19, 20, 21, 22
+OPT_SEEDS_LAYERED = 23
 MODE_LIST, MODE_PERSISTENT = 0, 1
 
 i64 = C.c_int64
@@ -243,6 +244,7 @@ def lib():
         L.eik_labels3d_dev.argtypes = [vp, vp, C.c_int, i64, i64, i64, _i64p, vp, i64, vp, vp]
         L.eik_tmap3d_seeds_f32.argtypes = [vp, _f32p, i64, i64, i64, _i64p, vp, i64, _f32p, vp]
         L.eik_tmap3d_seeds_f64.argtypes = [vp, _f64p, i64, i64, i64, _i64p, vp, i64, _f64p, vp]
+        L.eik_fim3d_last_solver.argtypes = [vp, _i64p]
         _lib = L
         return L
 
@@ -324,6 +326,7 @@ EXPORTED = [
     "eik_cost_diff_dev", "eik_fim2d_resolve_cost", "eik_fim2d_diff_info", "eik_tmap2d_update_cost_f32",
     "eik_tmap2d_update_cost_f64",
     "eik_fim3d_solve_seeds", "eik_labels3d_dev", "eik_tmap3d_seeds_f32", "eik_tmap3d_seeds_f64",
+    "eik_fim3d_last_solver",
 ]
 
 
@@ -398,6 +401,7 @@ class Context:
             raise EikError(rc, L.eik_last_error(None).decode())
         self._h = h
         self.device = device
+        self._set = {}  # option -> the last value set through this object (get_option)
         for name, val in parse_options(options).items():
             self.set_option(globals()["OPT_" + name], float(val))
 
@@ -419,6 +423,13 @@ class Context:
 
     def set_option(self, opt, value):
         self._chk(lib().eik_set_option(self._h, int(opt), float(value)))
+        self._set[int(opt)] = float(value)
+
+    def get_option(self, opt, default=None):
+        """The last value given to set_option for `opt` on this object (the library has no read-back), or
+        `default` -- the caller's knowledge of the library's default -- when it was never set: what a caller
+        that changes an option for one call puts back afterwards."""
+        return self._set.get(int(opt), default)
 
     def stats(self):
         s = EikStats()
@@ -628,8 +639,17 @@ class Context:
             self._chk(fn(self._h, cost, H, W, Lz, g, s, T))
         return T
 
+    def last_solver3d(self):
+        """What the last 3D solve on this context (tmap3d, tmap3d_seeds, fim3d_solve_seeds, ...) ran on
+        (eik_fim3d_last_solver): the layered solver or the general one, the first solved layer, the number
+        of solved layers (0 on the general solver), priority bands set up."""
+        out = np.zeros(4, np.int64)
+        self._chk(lib().eik_fim3d_last_solver(self._h, out))
+        return {"layered": int(out[0]), "z0": int(out[1]), "nl": int(out[2]), "bands": int(out[3])}
+
     # -- goal sets for 3D solves (eik_fim3d_solve_seeds, eik_labels3d_dev, eik_tmap3d_seeds_*): one
-    # volume on the general 3D solver, seeds K x (x, y, z), t0 their start values (None: all 0)
+    # volume, seeds K x (x, y, z), t0 their start values (None: all 0); on the general 3D solver, or with
+    # OPT_SEEDS_LAYERED on the layered one where eik_fim3d_solve's rule and the seeds' layers allow
     def tmap3d_seeds(self, cost, seeds, t0=None, dtype=np.float64, labels=False):
         """The field of a seed set in a volume cost[y, x, z] -> T, or (T, labels int32: the seed each cell
         belongs to, -1 = none) with labels=True."""
