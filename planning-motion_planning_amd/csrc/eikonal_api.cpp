@@ -817,6 +817,20 @@ int eik_fim2d_start(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
 }
 
 // ---- multi-source solves (seeds.hip)
+// Seed k's start value as the 2D and the 3D solvers take it (seeds_check, seeds3_check): finite and >= 0,
+// rounded to the dtype without reaching +inf, -0 as +0.
+static int seed_t0(eik_ctx* c, const char* who, const double* t0, int64_t k, bool f64, double* out) {
+    double v = t0 ? t0[k] : 0.0;
+    if (!(v >= 0.0) || std::isinf(v))
+        return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g (finite and >= 0 needed)", who, (long)k, v);
+    if (!f64) {
+        v = (double)(float)v;
+        if (std::isinf(v)) return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g rounds to +inf in fp32", who, (long)k, t0[k]);
+    }
+    *out = v + 0.0;  // (+ 0.0: -0 -> +0, values order like their bits)
+    return EIK_OK;
+}
+
 // The host checks shared by the seeded start and the labels: on EIK_OK out holds the K descriptors,
 // t0 rounded to the dtype.  Every failure is EIK_ERR_ARG with the offending index; nothing is launched.
 static int seeds_check(eik_ctx* c, const char* who, int64_t B, int64_t H, int64_t W, bool f64, const int64_t* seeds,
@@ -833,20 +847,17 @@ static int seeds_check(eik_ctx* c, const char* who, int64_t B, int64_t H, int64_
                            (long)W);
         const int32_t m = map_of ? map_of[k] : 0;
         if (m < 0 || m >= B) return set_err(c, EIK_ERR_ARG, "%s: map_of[%ld] = %d outside [0, %ld)", who, (long)k, m, (long)B);
-        double v = t0 ? t0[k] : 0.0;
-        if (!(v >= 0.0) || std::isinf(v))
-            return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g (finite and >= 0 needed)", who, (long)k, v);
-        if (!f64) {
-            v = (double)(float)v;
-            if (std::isinf(v)) return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g rounds to +inf in fp32", who, (long)k, t0[k]);
-        }
-        out[k] = SeedDesc{(int32_t)x, (int32_t)y, m, 0, v + 0.0};  // (+ 0.0: -0 -> +0, values order like their bits)
+        double v = 0.0;
+        const int rc = seed_t0(c, who, t0, k, f64, &v);
+        if (rc) return rc;
+        out[k] = SeedDesc{(int32_t)x, (int32_t)y, m, 0, v};
     }
     return EIK_OK;
 }
 
-int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
-                          const int32_t* map_of, int64_t K, void* stream) {
+// eik_fim2d_start_seeds' own checks: what it refuses, then the seeds into v
+static int start_seeds_check(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                             const int32_t* map_of, int64_t K, std::vector<SeedDesc>& v) {
     if (!f) return EIK_ERR_ARG;
     eik_ctx* c = f->ctx;
     const char* who = "eik_fim2d_start_seeds";
@@ -854,9 +865,14 @@ int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int
     if (f->lnl) return set_err(c, EIK_ERR_ARG, "%s: not for a layered block", who);
     if (f->a.ghost[0] || f->a.ghost[1] || f->a.ghost[2] || f->a.ghost[3])
         return set_err(c, EIK_ERR_ARG, "%s: not for a domain-decomposition block (ghost strips are bound)", who);
-    std::vector<SeedDesc> v;
-    int rc = seeds_check(c, who, f->B, f->H, f->W, f->f64, seeds, t0, map_of, K, v);
-    if (!rc) rc = fim2d_configure(f, d_cost, d_T, stream);
+    return seeds_check(c, who, f->B, f->H, f->W, f->f64, seeds, t0, map_of, K, v);
+}
+
+// The seeded start from checked descriptors.  v by value: it becomes the bound list, and a caller that starts
+// again from the bound list (solve_bound) passes f->bound itself.
+static int start_seeds_desc(eik_fim2d* f, const void* d_cost, void* d_T, std::vector<SeedDesc> v, void* stream) {
+    eik_ctx* c = f->ctx;
+    int rc = fim2d_configure(f, d_cost, d_T, stream);
     if (rc) return rc;
     // the ordinary init with no goal on any map (a goal outside the map seeds nothing), then the seeds
     std::vector<int64_t> none(2 * (size_t)f->B, -1);
@@ -864,12 +880,19 @@ int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int
     if (!rc) rc = seeds_upload(c, f->sd, v, f->stream);
     if (rc) return rc;
     HIPCHK(c, fim2d_init(f->a, f->f64, (int)f->B, (const int64_t*)f->goals.p, (unsigned*)f->edge.p, f->stream));
-    HIPCHK(c, fim2d_start_seeds(f->a, f->f64, f->sd.d, K, f->stream));
+    HIPCHK(c, fim2d_start_seeds(f->a, f->f64, f->sd.d, (int64_t)v.size(), f->stream));
     f->started = true;
     f->seeded = true;
     f->bound = std::move(v);
     f->need_rewind = false;  // the init cleared the queue words
     return EIK_OK;
+}
+
+int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
+                          const int32_t* map_of, int64_t K, void* stream) {
+    std::vector<SeedDesc> v;
+    const int rc = start_seeds_check(f, d_cost, d_T, seeds, t0, map_of, K, v);
+    return rc ? rc : start_seeds_desc(f, d_cost, d_T, std::move(v), stream);
 }
 
 // the persistent launch's queue words (h_q, read back after it): errors and the active count
@@ -1118,18 +1141,23 @@ static int finish_solve(eik_fim2d* f, int64_t* active) {
     return f->a.mode == kModePersistent ? persist_result(f, active) : EIK_OK;
 }
 
-int eik_fim2d_solve(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
+// One solve to convergence: start() binds the buffers and seeds the field (from goals or from a seed list;
+// it checks its own arguments, f among them), the iteration runs with the synchronisation deferred to the
+// finish.
+extern "C++" {
+template <typename Start>
+static int solve_loop(eik_fim2d* f, Start start) {
     int64_t active = 0;
     int rc = EIK_OK;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = eik_fim2d_start(f, d_cost, d_T, goals, stream);
+        rc = start();
         if (rc) return rc;
         f->defer_sync = f->a.mode == kModePersistent;
         rc = eik_fim2d_iterate(f, f->max_iters, &active);
         f->defer_sync = false;
         if (!rc) rc = finish_solve(f, &active);  // (the persistent launch's error word is read here)
         if (!(rc && f->band_overflow)) break;
-        // a priority band's ring was full: solve again from the start with the FIFO (this solver
+        // a priority band's ring was full: solve again from the same start with the FIFO (this solver
         // keeps it); finish_solve waited for the stream
         f->band_overflow = false;
         f->no_bands = true;
@@ -1140,27 +1168,50 @@ int eik_fim2d_solve(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
                        (long)f->iterations);
     return EIK_OK;
 }
+}  // extern "C++"
+
+int eik_fim2d_solve(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
+    return solve_loop(f, [&] { return eik_fim2d_start(f, d_cost, d_T, goals, stream); });
+}
+
+static int solve_seeds_desc(eik_fim2d* f, const void* d_cost, void* d_T, const std::vector<SeedDesc>& v, void* stream) {
+    return solve_loop(f, [&] { return start_seeds_desc(f, d_cost, d_T, v, stream); });
+}
 
 int eik_fim2d_solve_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0,
                           const int32_t* map_of, int64_t K, void* stream) {
-    int64_t active = 0;
-    int rc = EIK_OK;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        rc = eik_fim2d_start_seeds(f, d_cost, d_T, seeds, t0, map_of, K, stream);
-        if (rc) return rc;
-        f->defer_sync = f->a.mode == kModePersistent;
-        rc = eik_fim2d_iterate(f, f->max_iters, &active);
-        f->defer_sync = false;
-        if (!rc) rc = finish_solve(f, &active);
-        if (!(rc && f->band_overflow)) break;
-        // a priority band's ring was full: again from the same seeds on the FIFO, as eik_fim2d_solve
-        f->band_overflow = false;
-        f->no_bands = true;
-    }
+    std::vector<SeedDesc> v;
+    const int rc = start_seeds_check(f, d_cost, d_T, seeds, t0, map_of, K, v);
+    return rc ? rc : solve_seeds_desc(f, d_cost, d_T, v, stream);
+}
+
+// A solve from scratch from what the solver is bound to (one map: replan_gate passed): the goal of the last
+// start / adopt, or the bound seed list.
+static int solve_bound(eik_fim2d* f, const void* d_cost, void* d_T, void* stream) {
+    if (f->seeded) return solve_seeds_desc(f, d_cost, d_T, f->bound, stream);
+    const int64_t g[2] = {f->h_goals[0], f->h_goals[1]};  // (a copy: the start writes h_goals)
+    return eik_fim2d_solve(f, d_cost, d_T, g, stream);
+}
+
+// the labels from checked descriptors (fewer than 2^31 cells in all)
+static int labels2d_desc(eik_ctx* c, const void* d_T, bool f64, int64_t B, int64_t H, int64_t W, const std::vector<SeedDesc>& v,
+                         int32_t* d_label, hipStream_t st) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = B * H * W;
+    HIPCHK(c, c->lab_work.ensure(sizeof(int) * (size_t)n + sizeof(unsigned) * kLabelPasses));
+    const int rc = seeds_upload(c, c->lab_seeds, v, st);
     if (rc) return rc;
-    if (active != 0)
-        return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence after %ld iterations (negative costs?)",
-                       (long)f->iterations);
+    LabelArgs l{};
+    l.T = d_T;
+    l.H = H;
+    l.W = W;
+    l.n = n;
+    l.seeds = c->lab_seeds.d;
+    l.K = (int)v.size();
+    l.par = (int*)c->lab_work.p;
+    l.label = d_label;
+    l.flags = (unsigned*)(l.par + n);
+    HIPCHK(c, labels2d(l, f64, st));
     return EIK_OK;
 }
 
@@ -1175,26 +1226,8 @@ int eik_labels2d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t 
         return set_err(c, EIK_ERR_ARG, "%s: B = %ld maps of %ld x %ld (1 .. 2^31 - 1 cells in all)", who, (long)B, (long)H,
                        (long)W);
     std::vector<SeedDesc> v;
-    int rc = seeds_check(c, who, B, H, W, dtype == EIK_F64, seeds, t0, map_of, K, v);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = B * H * W;
-    HIPCHK(c, c->lab_work.ensure(sizeof(int) * (size_t)n + sizeof(unsigned) * kLabelPasses));
-    rc = seeds_upload(c, c->lab_seeds, v, st);
-    if (rc) return rc;
-    LabelArgs l{};
-    l.T = d_T;
-    l.H = H;
-    l.W = W;
-    l.n = n;
-    l.seeds = c->lab_seeds.d;
-    l.K = (int)K;
-    l.par = (int*)c->lab_work.p;
-    l.label = d_label;
-    l.flags = (unsigned*)(l.par + n);
-    HIPCHK(c, labels2d(l, dtype == EIK_F64, st));
-    return EIK_OK;
+    const int rc = seeds_check(c, who, B, H, W, dtype == EIK_F64, seeds, t0, map_of, K, v);
+    return rc ? rc : labels2d_desc(c, d_T, dtype == EIK_F64, B, H, W, v, d_label, (hipStream_t)stream);
 }
 
 // ---- incremental re-solve after local cost changes (replan.hip)
@@ -1266,73 +1299,106 @@ static int replan_rects_check(eik_fim2d* f, const char* who, const int64_t* rect
     return EIK_OK;
 }
 
-int eik_fim2d_update(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
-    if (!f) return EIK_ERR_ARG;
+// The state an update needs, after replan_gate: started or adopted, a binding the caller can re-solve
+// (wrong_binding: why it cannot, or NULL), the persistent mode, converged.
+static int replan_state(eik_fim2d* f, const char* who, const char* wrong_binding) {
     eik_ctx* c = f->ctx;
-    int rc = replan_gate(f, "eik_fim2d_update");
-    if (rc) return rc;
-    if (!f->started || !f->a.cost || !f->a.T)
-        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the solver was never started or adopted");
-    if (f->seeded)  // (the invalidation spares one goal, r.gx / r.gy: the other seeds would be reset)
-        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the bound solve has a seed set (eik_fim2d_start_seeds); start or "
-                                       "adopt a single-goal solve first");
-    if (f->a.mode != kModePersistent)
-        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the bound solve did not run in the persistent mode");
-    if (f->last_active != 0)
-        return set_err(c, EIK_ERR_ARG, "eik_fim2d_update: the last solve did not end converged (0 active tiles)");
-    std::vector<ReplanRect> v;
-    bool any = false;
-    rc = replan_rects_check(f, "eik_fim2d_update", rects, kinds, K, v, &any);
-    if (rc) return rc;
-    ReplanArgs r{};
-    rc = replan_buffers(f, &r);
-    // options, budgets and the priority bands (their width from the NEW cost) as eik_fim2d_start sets them
-    if (!rc) rc = fim2d_configure(f, f->a.cost, f->a.T, stream);
-    if (rc) return rc;
-    r.K = (int)K;
-    if (K > 0) {  // (the last update's copy has completed: a solve synchronised since)
-        memcpy(f->h_rects, v.data(), sizeof(ReplanRect) * (size_t)K);
-        HIPCHK(c, hipMemcpyAsync(f->rp_rects.p, f->h_rects, sizeof(ReplanRect) * (size_t)K, hipMemcpyHostToDevice, f->stream));
-    }
-    // the flood runs on the plain FIFO of the solver's queue
+    if (!f->started || !f->a.cost || !f->a.T) return set_err(c, EIK_ERR_ARG, "%s: the solver was never started or adopted", who);
+    if (wrong_binding) return set_err(c, EIK_ERR_ARG, "%s: %s", who, wrong_binding);
+    if (f->a.mode != kModePersistent) return set_err(c, EIK_ERR_ARG, "%s: the bound solve did not run in the persistent mode", who);
+    if (f->last_active != 0) return set_err(c, EIK_ERR_ARG, "%s: the last solve did not end converged (0 active tiles)", who);
+    return EIK_OK;
+}
+
+// an update's checked rectangles on the device (the last update's copy has completed: a solve synchronised since)
+static int replan_stage_rects(eik_fim2d* f, const std::vector<ReplanRect>& v) {
+    if (v.empty()) return EIK_OK;
+    memcpy(f->h_rects, v.data(), sizeof(ReplanRect) * v.size());
+    HIPCHK(f->ctx, hipMemcpyAsync(f->rp_rects.p, f->h_rects, sizeof(ReplanRect) * v.size(), hipMemcpyHostToDevice, f->stream));
+    return EIK_OK;
+}
+
+// the flood runs on the plain FIFO of the solver's queue
+static Fim2dArgs fifo_args(const eik_fim2d* f) {
     Fim2dArgs fa = f->a;
     fa.bctl = nullptr;
     fa.fresh_first = 0;
     fa.qhold = nullptr;
     fa.live = nullptr;
     fa.edge_dirty = nullptr;
-    HIPCHK(c, hipEventRecord(f->ev_rp[0], f->stream));
-    HIPCHK(c, replan_prep(fa, r, 0, f->stream));
-    if (any) {
-        if (f->flood_grid == 0) f->flood_grid = replan_flood_resident(f->f64, c->cu_count);
-        const int g = std::max(1, std::min(c->grid > 0 ? c->grid : 4 * c->cu_count, f->flood_grid));
-        HIPCHK(c, replan_seed(fa, r, f->f64, f->stream));
-        HIPCHK(c, replan_flood(fa, r, f->f64, g, f->stream));
-    }
-    HIPCHK(c, replan_prep(f->a, r, 1, f->stream));
-    if (K > 0) HIPCHK(c, replan_reset(f->a, r, f->f64, f->stream));
+    return fa;
+}
+
+// ... on the flood kernel's co-resident workgroups at most
+static int flood_grid(eik_fim2d* f) {
+    eik_ctx* c = f->ctx;
+    if (f->flood_grid == 0) f->flood_grid = replan_flood_resident(f->f64, c->cu_count);
+    return std::max(1, std::min(c->grid > 0 ? c->grid : 4 * c->cu_count, f->flood_grid));
+}
+
+// after an update's last kernel: its stop event and the counters' read-back
+static int replan_update_done(eik_fim2d* f) {
+    eik_ctx* c = f->ctx;
     HIPCHK(c, hipEventRecord(f->ev_rp[1], f->stream));
     HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
     f->rp_timed = true;
     f->rp_fallback = false;
     f->need_rewind = false;  // the prep cleared the queue words
+    return EIK_OK;
+}
+
+int eik_fim2d_update(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    eik_ctx* c = f->ctx;
+    const char* who = "eik_fim2d_update";
+    // (the invalidation spares one goal, r.gx / r.gy: the other seeds would be reset)
+    const char* seed_set = "the bound solve has a seed set (eik_fim2d_start_seeds); start or adopt a single-goal solve first";
+    int rc = replan_gate(f, who);
+    if (!rc) rc = replan_state(f, who, f->seeded ? seed_set : nullptr);
+    if (rc) return rc;
+    std::vector<ReplanRect> v;
+    bool any = false;
+    rc = replan_rects_check(f, who, rects, kinds, K, v, &any);
+    if (rc) return rc;
+    ReplanArgs r{};
+    rc = replan_buffers(f, &r);
+    // options, budgets and the priority bands (their width from the NEW cost) as eik_fim2d_start sets them
+    if (!rc) rc = fim2d_configure(f, f->a.cost, f->a.T, stream);
+    if (!rc) rc = replan_stage_rects(f, v);
+    if (rc) return rc;
+    r.K = (int)K;
+    const Fim2dArgs fa = fifo_args(f);
+    HIPCHK(c, hipEventRecord(f->ev_rp[0], f->stream));
+    HIPCHK(c, replan_prep(fa, r, 0, f->stream));
+    if (any) {
+        const int g = flood_grid(f);
+        HIPCHK(c, replan_seed(fa, r, f->f64, f->stream));
+        HIPCHK(c, replan_flood(fa, r, f->f64, g, f->stream));
+    }
+    HIPCHK(c, replan_prep(f->a, r, 1, f->stream));
+    if (K > 0) HIPCHK(c, replan_reset(f->a, r, f->f64, f->stream));
+    rc = replan_update_done(f);
+    if (rc) return rc;
     if (K == 0) f->last_active = 0;  // nothing queued: still converged
     return EIK_OK;
 }
 
-int eik_fim2d_resolve(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
-    int rc = eik_fim2d_update(f, rects, kinds, K, stream);
+// One re-solve: update() queues the tiles to re-solve (it checks its own arguments, f among them), the
+// iteration runs with the synchronisation deferred to the finish.
+extern "C++" {
+template <typename Update>
+static int resolve_loop(eik_fim2d* f, void* stream, Update update) {
+    int rc = update();
     if (rc) return rc;
     int64_t active = 0;
     f->defer_sync = true;
     rc = eik_fim2d_iterate(f, f->max_iters, &active);
     f->defer_sync = false;
     if (!rc) rc = finish_solve(f, &active);
-    if (rc && f->band_overflow) {  // a priority band's ring was full: a full solve on the FIFO
+    if (rc && f->band_overflow) {  // a priority band's ring was full: a full solve on the FIFO (a seed set: the new list)
         f->band_overflow = false;
         f->no_bands = true;
-        const int64_t g[2] = {f->h_goals[0], f->h_goals[1]};
-        rc = eik_fim2d_solve(f, f->a.cost, f->a.T, g, stream);
+        rc = solve_bound(f, f->a.cost, f->a.T, stream);
         f->rp_fallback = true;
         return rc;
     }
@@ -1341,15 +1407,18 @@ int eik_fim2d_resolve(eik_fim2d* f, const int64_t* rects, const int* kinds, int6
         return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence of the re-solve (%ld tiles left; negative costs?)", (long)active);
     return EIK_OK;
 }
+}  // extern "C++"
 
-int eik_fim2d_adopt(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
-    if (!f) return EIK_ERR_ARG;
+int eik_fim2d_resolve(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, void* stream) {
+    return resolve_loop(f, stream, [&] { return eik_fim2d_update(f, rects, kinds, K, stream); });
+}
+
+// Adopt's launches, after its checks and the goals' upload: the field's marks and the queue as after a
+// converged solve.  (What the field is bound to is the caller's to set.)
+static int adopt_bound(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
     eik_ctx* c = f->ctx;
-    if (!d_cost || !d_T || !goals) return set_err(c, EIK_ERR_ARG, "eik_fim2d_adopt: NULL argument");
-    int rc = replan_gate(f, "eik_fim2d_adopt");
-    if (rc) return rc;
     ReplanArgs r{};
-    rc = replan_buffers(f, &r);
+    int rc = replan_buffers(f, &r);
     if (!rc) rc = fim2d_configure(f, d_cost, d_T, stream);
     if (!rc) rc = upload_goals(f, goals);
     if (rc) return rc;
@@ -1359,13 +1428,32 @@ int eik_fim2d_adopt(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* 
     f->rp_timed = false;
     f->rp_fallback = false;
     f->started = true;
-    f->seeded = false;
     f->need_rewind = false;
     f->last_active = 0;
     return EIK_OK;
 }
 
+int eik_fim2d_adopt(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* goals, void* stream) {
+    if (!f) return EIK_ERR_ARG;
+    if (!d_cost || !d_T || !goals) return set_err(f->ctx, EIK_ERR_ARG, "eik_fim2d_adopt: NULL argument");
+    int rc = replan_gate(f, "eik_fim2d_adopt");
+    if (!rc) rc = adopt_bound(f, d_cost, d_T, goals, stream);
+    if (rc) return rc;
+    f->seeded = false;
+    return EIK_OK;
+}
+
 // ---- the re-solve of a seeded field: cost and seed-list changes (replan.hip)
+// adopt from a checked list (replan_gate passed)
+static int adopt_seeds_desc(eik_fim2d* f, const void* d_cost, void* d_T, std::vector<SeedDesc> v, void* stream) {
+    const int64_t none[2] = {-1, -1};  // no goal, as after eik_fim2d_start_seeds
+    const int rc = adopt_bound(f, d_cost, d_T, none, stream);
+    if (rc) return rc;
+    f->seeded = true;
+    f->bound = std::move(v);
+    return EIK_OK;
+}
+
 int eik_fim2d_adopt_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int64_t* seeds, const double* t0, int64_t Ks,
                           void* stream) {
     if (!f) return EIK_ERR_ARG;
@@ -1376,49 +1464,26 @@ int eik_fim2d_adopt_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int
     if (rc) return rc;
     std::vector<SeedDesc> v;
     rc = seeds_check(c, who, 1, f->H, f->W, f->f64, seeds, t0, nullptr, Ks, v);
-    if (rc) return rc;
-    ReplanArgs r{};
-    rc = replan_buffers(f, &r);
-    if (!rc) rc = fim2d_configure(f, d_cost, d_T, stream);
-    const int64_t none[2] = {-1, -1};  // no goal, as after eik_fim2d_start_seeds
-    if (!rc) rc = upload_goals(f, none);
-    if (rc) return rc;
-    HIPCHK(c, replan_adopt(f->a, f->f64, f->stream));
-    HIPCHK(c, replan_prep(f->a, r, 0, f->stream));  // the queue as after a converged solve
-    HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
-    f->rp_timed = false;
-    f->rp_fallback = false;
-    f->started = true;
-    f->seeded = true;
-    f->bound = std::move(v);
-    f->need_rewind = false;
-    f->last_active = 0;
-    return EIK_OK;
+    return rc ? rc : adopt_seeds_desc(f, d_cost, d_T, std::move(v), stream);
 }
 
-int eik_fim2d_update_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
-                           const double* t0, int64_t Ks, void* stream) {
+static const char* const kUpdateSeeds = "eik_fim2d_update_seeds";
+
+// eik_fim2d_update_seeds' checks before the new list's: what it refuses, then the rectangles into v
+static int update_seeds_check(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, std::vector<ReplanRect>& v,
+                              bool* any) {
     if (!f) return EIK_ERR_ARG;
+    const char* single = "the bound solve has a single goal: eik_fim2d_update, or eik_fim2d_adopt_seeds first";
+    int rc = replan_gate(f, kUpdateSeeds);
+    if (!rc) rc = replan_state(f, kUpdateSeeds, !f->seeded || f->bound.empty() ? single : nullptr);
+    return rc ? rc : replan_rects_check(f, kUpdateSeeds, rects, kinds, K, v, any);
+}
+
+// The seeded update from checked rectangles and a checked new list (nw by value: it becomes the bound list,
+// and a caller whose list stays passes f->bound itself): the diff of nw against the bound list, then the launches.
+static int update_seeds_desc(eik_fim2d* f, const std::vector<ReplanRect>& v, bool any, std::vector<SeedDesc> nw, void* stream) {
     eik_ctx* c = f->ctx;
-    const char* who = "eik_fim2d_update_seeds";
-    int rc = replan_gate(f, who);
-    if (rc) return rc;
-    if (!f->started || !f->a.cost || !f->a.T) return set_err(c, EIK_ERR_ARG, "%s: the solver was never started or adopted", who);
-    if (!f->seeded || f->bound.empty())
-        return set_err(c, EIK_ERR_ARG, "%s: the bound solve has a single goal: eik_fim2d_update, or eik_fim2d_adopt_seeds first", who);
-    if (f->a.mode != kModePersistent) return set_err(c, EIK_ERR_ARG, "%s: the bound solve did not run in the persistent mode", who);
-    if (f->last_active != 0) return set_err(c, EIK_ERR_ARG, "%s: the last solve did not end converged (0 active tiles)", who);
-    std::vector<ReplanRect> v;
-    bool any = false;
-    rc = replan_rects_check(f, who, rects, kinds, K, v, &any);
-    if (rc) return rc;
-    // the new list (seeds == NULL with Ks == 0: the bound one stays) and its diff against the bound one
-    std::vector<SeedDesc> nw;
-    if (!seeds && Ks == 0)
-        nw = f->bound;
-    else
-        rc = seeds_check(c, who, 1, f->H, f->W, f->f64, seeds, t0, nullptr, Ks, nw);
-    if (rc) return rc;
+    const int64_t K = (int64_t)v.size();
     std::vector<SeedCell> co(f->bound.size()), cn(nw.size());
     for (size_t k = 0; k < co.size(); ++k) co[k] = SeedCell{f->bound[k].x, f->bound[k].y, f->bound[k].t0};
     for (size_t k = 0; k < cn.size(); ++k) cn[k] = SeedCell{nw[k].x, nw[k].y, nw[k].t0};
@@ -1426,31 +1491,20 @@ int eik_fim2d_update_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds,
     const SeedDiff diff = seed_diff(co.data(), (int64_t)co.size(), cn.data(), (int64_t)cn.size(), roots);
     const bool flood = any || diff.released > 0;  // there is a cone to find: the roots take part
     ReplanArgs r{};
-    rc = replan_buffers(f, &r);
+    int rc = replan_buffers(f, &r);
     // options, budgets and the priority bands (their width from the NEW cost) as eik_fim2d_start sets them
     if (!rc) rc = fim2d_configure(f, f->a.cost, f->a.T, stream);
-    if (rc) return rc;
-    r.K = (int)K;
-    if (K > 0) {
-        memcpy(f->h_rects, v.data(), sizeof(ReplanRect) * (size_t)K);
-        HIPCHK(c, hipMemcpyAsync(f->rp_rects.p, f->h_rects, sizeof(ReplanRect) * (size_t)K, hipMemcpyHostToDevice, f->stream));
-    }
-    if (flood) rc = seeds_upload(c, f->roots, roots, f->stream);
+    if (!rc) rc = replan_stage_rects(f, v);
+    if (!rc && flood) rc = seeds_upload(c, f->roots, roots, f->stream);
     if (!rc) rc = seeds_upload(c, f->sd, nw, f->stream);
     if (rc) return rc;
-    // the flood runs on the plain FIFO of the solver's queue
-    Fim2dArgs fa = f->a;
-    fa.bctl = nullptr;
-    fa.fresh_first = 0;
-    fa.qhold = nullptr;
-    fa.live = nullptr;
-    fa.edge_dirty = nullptr;
+    r.K = (int)K;
+    const Fim2dArgs fa = fifo_args(f);
     const int64_t nroots = (int64_t)roots.size();
     HIPCHK(c, hipEventRecord(f->ev_rp[0], f->stream));
     HIPCHK(c, replan_prep(fa, r, 0, f->stream));
     if (flood) {
-        if (f->flood_grid == 0) f->flood_grid = replan_flood_resident(f->f64, c->cu_count);
-        const int g = std::max(1, std::min(c->grid > 0 ? c->grid : 4 * c->cu_count, f->flood_grid));
+        const int g = flood_grid(f);
         HIPCHK(c, replan_roots(fa, r, f->f64, f->roots.d, nroots, f->stream));
         HIPCHK(c, replan_seed(fa, r, f->f64, f->stream));
         HIPCHK(c, replan_flood(fa, r, f->f64, g, f->stream));
@@ -1460,44 +1514,39 @@ int eik_fim2d_update_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds,
     if (K > 0 || diff.released > 0) HIPCHK(c, replan_reset(f->a, r, f->f64, f->stream));
     // (always: a dominated seed of an unchanged list may lie in the cone, and is put back at its t0)
     HIPCHK(c, replan_reseed(f->a, r, f->f64, f->sd.d, (int64_t)nw.size(), f->stream));
-    HIPCHK(c, hipEventRecord(f->ev_rp[1], f->stream));
-    HIPCHK(c, hipMemcpyAsync(f->h_info, f->rp_info.p, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
-    f->rp_timed = true;
-    f->rp_fallback = false;
-    f->need_rewind = false;  // the prep cleared the queue words
+    rc = replan_update_done(f);
+    if (rc) return rc;
     f->bound = std::move(nw);
     if (K == 0 && diff.same) f->last_active = 0;  // nothing queued: still converged
     return EIK_OK;
 }
 
+int eik_fim2d_update_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
+                           const double* t0, int64_t Ks, void* stream) {
+    std::vector<ReplanRect> v;
+    bool any = false;
+    int rc = update_seeds_check(f, rects, kinds, K, v, &any);
+    if (rc) return rc;
+    if (!seeds && Ks == 0) return update_seeds_desc(f, v, any, f->bound, stream);  // the bound list stays
+    std::vector<SeedDesc> nw;
+    rc = seeds_check(f->ctx, kUpdateSeeds, 1, f->H, f->W, f->f64, seeds, t0, nullptr, Ks, nw);
+    return rc ? rc : update_seeds_desc(f, v, any, std::move(nw), stream);
+}
+
 int eik_fim2d_resolve_seeds(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, const int64_t* seeds,
                             const double* t0, int64_t Ks, void* stream) {
-    int rc = eik_fim2d_update_seeds(f, rects, kinds, K, seeds, t0, Ks, stream);
-    if (rc) return rc;
-    int64_t active = 0;
-    f->defer_sync = true;
-    rc = eik_fim2d_iterate(f, f->max_iters, &active);
-    f->defer_sync = false;
-    if (!rc) rc = finish_solve(f, &active);
-    if (rc && f->band_overflow) {  // a priority band's ring was full: a full seeded solve on the FIFO, the new list
-        f->band_overflow = false;
-        f->no_bands = true;
-        const std::vector<SeedDesc> b = f->bound;
-        std::vector<int64_t> s(2 * b.size());
-        std::vector<double> t(b.size());
-        for (size_t k = 0; k < b.size(); ++k) {
-            s[2 * k] = b[k].x;
-            s[2 * k + 1] = b[k].y;
-            t[k] = b[k].t0;
-        }
-        rc = eik_fim2d_solve_seeds(f, f->a.cost, f->a.T, s.data(), t.data(), nullptr, (int64_t)b.size(), stream);
-        f->rp_fallback = true;
-        return rc;
-    }
-    if (rc) return rc;
-    if (active != 0)
-        return set_err(f->ctx, EIK_ERR_NOCONVERGE, "no convergence of the re-solve (%ld tiles left; negative costs?)", (long)active);
-    return EIK_OK;
+    return resolve_loop(f, stream, [&] { return eik_fim2d_update_seeds(f, rects, kinds, K, seeds, t0, Ks, stream); });
+}
+
+// ... with a checked new list (nw == NULL: the bound list stays)
+static int resolve_seeds_desc(eik_fim2d* f, const int64_t* rects, const int* kinds, int64_t K, const std::vector<SeedDesc>* nw,
+                              void* stream) {
+    return resolve_loop(f, stream, [&] {
+        std::vector<ReplanRect> v;
+        bool any = false;
+        const int rc = update_seeds_check(f, rects, kinds, K, v, &any);
+        return rc ? rc : update_seeds_desc(f, v, any, nw ? *nw : f->bound, stream);
+    });
 }
 
 int eik_fim2d_update_info(eik_fim2d* f, int64_t out[6]) {
@@ -1642,11 +1691,8 @@ int eik_fim2d_resolve_cost(eik_fim2d* f, const void* d_cost_new, void* stream) {
     if (!d_cost_new) return set_err(c, EIK_ERR_ARG, "%s: d_cost_new is NULL", who);
     // what eik_fim2d_update / eik_fim2d_update_seeds refuse, before anything is launched or rebound
     int rc = replan_gate(f, who);
+    if (!rc) rc = replan_state(f, who, f->seeded && f->bound.empty() ? "the bound seed list is empty" : nullptr);
     if (rc) return rc;
-    if (!f->started || !f->a.cost || !f->a.T) return set_err(c, EIK_ERR_ARG, "%s: the solver was never started or adopted", who);
-    if (f->seeded && f->bound.empty()) return set_err(c, EIK_ERR_ARG, "%s: the bound seed list is empty", who);
-    if (f->a.mode != kModePersistent) return set_err(c, EIK_ERR_ARG, "%s: the bound solve did not run in the persistent mode", who);
-    if (f->last_active != 0) return set_err(c, EIK_ERR_ARG, "%s: the last solve did not end converged (0 active tiles)", who);
     hipStream_t st = (hipStream_t)stream;
     DiffHeader h{};
     int64_t us = 0;
@@ -1662,23 +1708,10 @@ int eik_fim2d_resolve_cost(eik_fim2d* f, const void* d_cost_new, void* stream) {
     di[6] = di[7] = 0;
     if (h.invalid > 0) return diff_invalid_error(f, d_cost_new, h, st);
     const double share = c->diff_share >= 0 ? c->diff_share : kDiffFullShare;
-    void* d_T = f->a.T;
     if ((int64_t)h.tiles > kDiffMinTiles && (double)h.tiles > share * (double)f->a.capacity) {
         // the share rule: most of the raster changed, the solve from scratch is the faster one (no list is built)
         di[6] = 1;
-        if (!f->seeded) {
-            const int64_t g[2] = {f->h_goals[0], f->h_goals[1]};
-            return eik_fim2d_solve(f, d_cost_new, d_T, g, stream);
-        }
-        const std::vector<SeedDesc> b = f->bound;
-        std::vector<int64_t> s(2 * b.size());
-        std::vector<double> t(b.size());
-        for (size_t k = 0; k < b.size(); ++k) {
-            s[2 * k] = b[k].x;
-            s[2 * k + 1] = b[k].y;
-            t[k] = b[k].t0;
-        }
-        return eik_fim2d_solve_seeds(f, d_cost_new, d_T, s.data(), t.data(), nullptr, (int64_t)b.size(), stream);
+        return solve_bound(f, d_cost_new, f->a.T, stream);
     }
     std::vector<int64_t> rects;
     std::vector<int> kinds;
@@ -2041,6 +2074,32 @@ static int check_cost(eik_ctx* c, const R* cost, const void* dev, int64_t n, hip
     return EIK_OK;
 }
 
+// The host entries' inputs of n cells on the device, in stream order: cost_old (optional) in c->cost2, cost in
+// c->cost, T_in (optional: a field to re-solve) in c->T, which is made in any case; labels: c->lab_out too.
+template <typename R>
+static int stage_inputs(eik_ctx* c, int64_t n, const R* cost, bool labels = false, const R* T_in = nullptr,
+                        const R* cost_old = nullptr) {
+    const size_t bytes = sizeof(R) * n;
+    HIPCHK(c, c->cost.ensure(bytes));
+    if (cost_old) HIPCHK(c, c->cost2.ensure(bytes));
+    HIPCHK(c, c->T.ensure(bytes));
+    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
+    if (cost_old) HIPCHK(c, host_to_dev(c, c->cost2.p, cost_old, bytes, c->stream));
+    HIPCHK(c, host_to_dev(c, c->cost.p, cost, bytes, c->stream));
+    if (T_in) HIPCHK(c, host_to_dev(c, c->T.p, T_in, bytes, c->stream));
+    return EIK_OK;
+}
+
+// ... and their results back: the field of n cells at d_T, the labels (optional) of c->lab_out, then the
+// stream synchronised
+template <typename R>
+static int fetch_results(eik_ctx* c, int64_t n, R* T, const void* d_T, int32_t* labels = nullptr) {
+    HIPCHK(c, dev_to_host(c, T, d_T, sizeof(R) * n, c->stream));
+    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EIK_OK;
+}
+
 template <typename R>
 static int tmap_host(eik_ctx* c, const R* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals, R* T) {
     if (!c || !cost || !T || !goals || B < 1 || H < 1 || W < 1) return c ? set_err(c, EIK_ERR_ARG, "bad arguments") : EIK_ERR_ARG;
@@ -2052,17 +2111,10 @@ static int tmap_host(eik_ctx* c, const R* cost, int64_t B, int64_t H, int64_t W,
     HIPCHK(c, hipSetDevice(c->device));
     eik_fim2d* f = nullptr;
     int rc = get_solver(c, B, H, W, sizeof(R) == 8 ? EIK_F64 : EIK_F32, &f);
-    if (rc) return rc;
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
-    rc = check_cost(c, cost, c->cost.p, n, c->stream);
-    if (rc) return rc;
-    rc = eik_fim2d_solve(f, c->cost.p, c->T.p, goals, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    if (!rc) rc = stage_inputs(c, n, cost);
+    if (!rc) rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = eik_fim2d_solve(f, c->cost.p, c->T.p, goals, c->stream);
+    return rc ? rc : fetch_results(c, n, T, c->T.p);
 }
 
 // cost_new and the converged field of the earlier cost go up; adopt + resolve on the cached solver
@@ -2081,19 +2133,12 @@ static int tmap_update_host(eik_ctx* c, const R* cost, R* T, int64_t H, int64_t 
     if (f->seeded)  // (T is most likely that solve's field, which one goal does not describe)
         return set_err(c, EIK_ERR_ARG, "eik_tmap2d_update: the bound solve has a seed set (eik_tmap2d_seeds); run a "
                                        "single-goal solve first");
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
-    HIPCHK(c, host_to_dev(c, c->T.p, T, sizeof(R) * n, c->stream));
-    rc = check_cost(c, cost, c->cost.p, n, c->stream);
-    if (rc) return rc;
+    rc = stage_inputs(c, n, cost, false, T);
+    if (!rc) rc = check_cost(c, cost, c->cost.p, n, c->stream);
     const int64_t g[2] = {gx, gy};
-    rc = eik_fim2d_adopt(f, c->cost.p, c->T.p, g, c->stream);
+    if (!rc) rc = eik_fim2d_adopt(f, c->cost.p, c->T.p, g, c->stream);
     if (!rc) rc = eik_fim2d_resolve(f, rects, kinds, K, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    return rc ? rc : fetch_results(c, n, T, c->T.p);
 }
 
 // both costs and the converged field of cost_old go up; adopt on cost_old, then the diff names what changed
@@ -2113,19 +2158,11 @@ static int tmap_update_cost_host(eik_ctx* c, const R* cost_old, const R* cost_ne
     int rc = get_solver(c, 1, H, W, sizeof(R) == 8 ? EIK_F64 : EIK_F32, &f);
     if (!rc) rc = replan_gate(f, who);
     if (rc) return rc;
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->cost2.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    HIPCHK(c, host_to_dev(c, c->cost2.p, cost_old, sizeof(R) * n, c->stream));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost_new, sizeof(R) * n, c->stream));
-    HIPCHK(c, host_to_dev(c, c->T.p, T, sizeof(R) * n, c->stream));
+    rc = stage_inputs(c, n, cost_new, false, T, cost_old);
     const int64_t g[2] = {gx, gy};
-    rc = eik_fim2d_adopt(f, c->cost2.p, c->T.p, g, c->stream);
+    if (!rc) rc = eik_fim2d_adopt(f, c->cost2.p, c->T.p, g, c->stream);
     if (!rc) rc = eik_fim2d_resolve_cost(f, c->cost.p, c->stream);  // (it checks cost_new: NaN or negative is EIK_ERR_ARG)
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    return rc ? rc : fetch_results(c, n, T, c->T.p);
 }
 
 // one map from a seed set on the cached solver; labels (optional) from the field while it is on the device
@@ -2136,7 +2173,7 @@ static int tmap_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, cons
     if (!cost || !T) return set_err(c, EIK_ERR_ARG, "eik_tmap2d_seeds: %s is NULL", !cost ? "cost" : "T");
     if (H < 1 || W < 1) return set_err(c, EIK_ERR_ARG, "eik_tmap2d_seeds: bad shape %ld x %ld", (long)H, (long)W);
     constexpr int dtype = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
-    std::vector<SeedDesc> v;  // (checked before anything is uploaded; the entry points below check again)
+    std::vector<SeedDesc> v;  // (checked once, before anything is uploaded: the solve and the labels take the descriptors)
     int rc = seeds_check(c, "eik_tmap2d_seeds", 1, H, W, sizeof(R) == 8, seeds, t0, nullptr, K, v);
     if (rc) return rc;
     if (labels && H * W >= (1ll << 31)) return set_err(c, EIK_ERR_ARG, "eik_tmap2d_seeds: labels need fewer than 2^31 cells");
@@ -2144,19 +2181,11 @@ static int tmap_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, cons
     HIPCHK(c, hipSetDevice(c->device));
     eik_fim2d* f = nullptr;
     rc = get_solver(c, 1, H, W, dtype, &f);
-    if (rc) return rc;
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
-    rc = check_cost(c, cost, c->cost.p, n, c->stream);
-    if (!rc) rc = eik_fim2d_solve_seeds(f, c->cost.p, c->T.p, seeds, t0, nullptr, K, c->stream);
-    if (!rc && labels) rc = eik_labels2d_dev(c, c->T.p, dtype, 1, H, W, seeds, t0, nullptr, K, (int32_t*)c->lab_out.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
-    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    if (!rc) rc = stage_inputs(c, n, cost, labels != nullptr);
+    if (!rc) rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = solve_seeds_desc(f, c->cost.p, c->T.p, v, c->stream);
+    if (!rc && labels) rc = labels2d_desc(c, c->T.p, sizeof(R) == 8, 1, H, W, v, (int32_t*)c->lab_out.p, c->stream);
+    return rc ? rc : fetch_results(c, n, T, c->T.p, labels);
 }
 
 // cost_new and the converged field of the earlier cost and the old list go up; adopt_seeds + resolve_seeds
@@ -2170,10 +2199,10 @@ static int tmap_update_seeds_host(eik_ctx* c, const R* cost, R* T, int64_t H, in
     if (!cost || !T) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !cost ? "cost_new" : "T_inout");
     if (H < 1 || W < 1) return set_err(c, EIK_ERR_ARG, "%s: bad shape %ld x %ld", who, (long)H, (long)W);
     constexpr int dtype = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
-    std::vector<SeedDesc> v;  // (checked before anything is uploaded; the entry points below check again)
-    int rc = seeds_check(c, who, 1, H, W, sizeof(R) == 8, seeds_old, t0_old, nullptr, K_old, v);
+    std::vector<SeedDesc> old, nw;  // (checked once, before anything is uploaded: adopt, resolve and the labels take the descriptors)
+    int rc = seeds_check(c, who, 1, H, W, sizeof(R) == 8, seeds_old, t0_old, nullptr, K_old, old);
     const bool keep = !seeds_new && K_new == 0;  // the list is unchanged
-    if (!rc && !keep) rc = seeds_check(c, who, 1, H, W, sizeof(R) == 8, seeds_new, t0_new, nullptr, K_new, v);
+    if (!rc && !keep) rc = seeds_check(c, who, 1, H, W, sizeof(R) == 8, seeds_new, t0_new, nullptr, K_new, nw);
     if (rc) return rc;
     if (labels && H * W >= (1ll << 31)) return set_err(c, EIK_ERR_ARG, "%s: labels need fewer than 2^31 cells", who);
     const int64_t n = H * W;
@@ -2181,23 +2210,12 @@ static int tmap_update_seeds_host(eik_ctx* c, const R* cost, R* T, int64_t H, in
     eik_fim2d* f = nullptr;
     rc = get_solver(c, 1, H, W, dtype, &f);
     if (!rc) rc = replan_gate(f, who);
-    if (rc) return rc;
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
-    HIPCHK(c, host_to_dev(c, c->T.p, T, sizeof(R) * n, c->stream));
-    rc = check_cost(c, cost, c->cost.p, n, c->stream);
-    if (!rc) rc = eik_fim2d_adopt_seeds(f, c->cost.p, c->T.p, seeds_old, t0_old, K_old, c->stream);
-    if (!rc) rc = eik_fim2d_resolve_seeds(f, rects, kinds, K, seeds_new, t0_new, K_new, c->stream);
-    if (!rc && labels)
-        rc = eik_labels2d_dev(c, c->T.p, dtype, 1, H, W, keep ? seeds_old : seeds_new, keep ? t0_old : t0_new, nullptr,
-                              keep ? K_old : K_new, (int32_t*)c->lab_out.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
-    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    if (!rc) rc = stage_inputs(c, n, cost, labels != nullptr, T);
+    if (!rc) rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = adopt_seeds_desc(f, c->cost.p, c->T.p, old, c->stream);
+    if (!rc) rc = resolve_seeds_desc(f, rects, kinds, K, keep ? nullptr : &nw, c->stream);
+    if (!rc && labels) rc = labels2d_desc(c, c->T.p, sizeof(R) == 8, 1, H, W, keep ? old : nw, (int32_t*)c->lab_out.p, c->stream);
+    return rc ? rc : fetch_results(c, n, T, c->T.p, labels);
 }
 
 extern "C" {
@@ -2869,6 +2887,24 @@ int eik_plan2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, in
 }
 
 // ------------------------------------------------------------------------------ 3D
+// How one persistent launch of a 3D driver ended, after its synchronisation: the queue error word's refusal
+// (who names the solver, budget_who prefixes the visit budget's text), else c->last's fields that both
+// drivers fill alike -- inplace_passes, fresh_visits and bytes_alg are the caller's.
+static int persist3_outcome(eik_ctx* c, unsigned err, const char* who, const char* budget_who, unsigned long long qbudget,
+                            hipEvent_t e0, hipEvent_t e1, unsigned long long visits) {
+    if (err & 1u) return set_err(c, EIK_ERR_HIP, "%s: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", who, c->qtimeout_s);
+    if (err & 2u)
+        return set_err(c, EIK_ERR_NOCONVERGE, "%sno convergence within %llu tile visits (negative costs?)", budget_who, qbudget);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    c->last = eik_stats{};
+    c->last.iterations = 1;
+    c->last.host_syncs = 1;
+    c->last.tile_visits = (int64_t)visits;
+    c->last.solve_ms = ms;
+    return EIK_OK;
+}
+
 // Few-layer fp32 volumes (the rover's (x, y, mode) costmaps) on the layered 2D-tile solver:
 // layers z0 .. z0+nl-1 of a [H][W][L] volume, one persistent launch.
 // d_seeds: a seed set in place of the goal (fim2dl_init_seeds; every seed's z in [z0, z0 + nl), goal unused).
@@ -2923,54 +2959,44 @@ static int solve_layered(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, i
     unsigned err = 0;
     // attempt 1 without bands when attempt 0's band ring overflowed (qerror bit 4, as eik_fim2d_solve)
     for (int attempt = 0; attempt < 2; ++attempt) {
-    HIPCHK(c, hipEventRecord(f->ev_start, st));
-    HIPCHK(c, hipMemsetAsync((void*)f->a.visits, 0, 3 * sizeof(unsigned long long), st));
-    if (planar) HIPCHK(c, layer_planar(d_cost, c->lp_cost.p, f64, H * W, L, z0, nl, true, st));
-    // priority bands (fim_engine.hpp), as eik_fim2d_start sets them up: on an explicit EIK_OPT_PRIO
-    a.bctl = nullptr;
-    const double prio = c->prio < 0 ? default_prio(H, W, 3072.0) : c->prio;
-    if (prio > 0 && attempt == 0 && a.capacity < (1 << kBandTagShift) - 1) {
-        HIPCHK(c, setup_bands(c, f->bslot, f->bctl, a.capacity, a, st));
-        HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)a.key, 0x7f800000u, (size_t)a.capacity, st));  // keys: +inf
-        float* pd = (float*)((char*)f->bctl.p + 128 * kBands);
-        HIPCHK(c, fim2d_prio_delta(a.cost, f64, planar ? (int64_t)nl * H * W : H * W * L, (float)prio, pd, st));
-        a.pdelta = pd;
-        // the dispatch batch: 32 below kWideTiles tiles (C5 16 / 32 / 48 / 64: fp64 3.61 / 3.67-3.69 / 3.65 /
-        // 3.58, fp32 6.30-6.33 / 6.37-6.38 / 6.27 / 6.08-6.12 Gcells/s, profiles/r05ak_layered_dispatch_ab.log)
-        a.disp = c->prio_dispatch > 0 ? (unsigned)c->prio_dispatch : a.tiles_per_map >= kWideTiles ? 64u : 32u;
-    }
-    if (d_seeds) {
-        HIPCHK(c, fim2dl_init_seeds(a, f64, d_seeds, K, z0, nT, st));
-    } else {
-        HIPCHK(c, fim2dl_init(a, f64, goal[0], goal[1], goal[2] - z0, nT, st));
-    }
-    HIPCHK(c, fim2dl_persist(a, nl, f64, grid, st));
-    if (planar) HIPCHK(c, layer_planar(c->lp_T.p, d_T, f64, H * W, L, z0, nl, false, st));
-    HIPCHK(c, hipEventRecord(f->ev_stop, st));
-    HIPCHK(c, hipMemcpyAsync(f->h_q, f->qctl.p, kQueueCtlBytes, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(f->h_visits, (void*)f->a.visits, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    err = f->h_q[192 / 4];
-    if (!(err & 4u) || (err & 3u)) break;
+        HIPCHK(c, hipEventRecord(f->ev_start, st));
+        HIPCHK(c, hipMemsetAsync((void*)f->a.visits, 0, 3 * sizeof(unsigned long long), st));
+        if (planar) HIPCHK(c, layer_planar(d_cost, c->lp_cost.p, f64, H * W, L, z0, nl, true, st));
+        // priority bands (fim_engine.hpp), as eik_fim2d_start sets them up: on an explicit EIK_OPT_PRIO
+        a.bctl = nullptr;
+        const double prio = c->prio < 0 ? default_prio(H, W, 3072.0) : c->prio;
+        if (prio > 0 && attempt == 0 && a.capacity < (1 << kBandTagShift) - 1) {
+            HIPCHK(c, setup_bands(c, f->bslot, f->bctl, a.capacity, a, st));
+            HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)a.key, 0x7f800000u, (size_t)a.capacity, st));  // keys: +inf
+            float* pd = (float*)((char*)f->bctl.p + 128 * kBands);
+            HIPCHK(c, fim2d_prio_delta(a.cost, f64, planar ? (int64_t)nl * H * W : H * W * L, (float)prio, pd, st));
+            a.pdelta = pd;
+            // the dispatch batch: 32 below kWideTiles tiles (C5 16 / 32 / 48 / 64: fp64 3.61 / 3.67-3.69 / 3.65 /
+            // 3.58, fp32 6.30-6.33 / 6.37-6.38 / 6.27 / 6.08-6.12 Gcells/s, profiles/r05ak_layered_dispatch_ab.log)
+            a.disp = c->prio_dispatch > 0 ? (unsigned)c->prio_dispatch : a.tiles_per_map >= kWideTiles ? 64u : 32u;
+        }
+        if (d_seeds) {
+            HIPCHK(c, fim2dl_init_seeds(a, f64, d_seeds, K, z0, nT, st));
+        } else {
+            HIPCHK(c, fim2dl_init(a, f64, goal[0], goal[1], goal[2] - z0, nT, st));
+        }
+        HIPCHK(c, fim2dl_persist(a, nl, f64, grid, st));
+        if (planar) HIPCHK(c, layer_planar(c->lp_T.p, d_T, f64, H * W, L, z0, nl, false, st));
+        HIPCHK(c, hipEventRecord(f->ev_stop, st));
+        HIPCHK(c, hipMemcpyAsync(f->h_q, f->qctl.p, kQueueCtlBytes, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(f->h_visits, (void*)f->a.visits, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        err = f->h_q[192 / 4];
+        if (!(err & 4u) || (err & 3u)) break;
     }
     c->last_solver3[0] = 1;  // eik_fim3d_last_solver
     c->last_solver3[1] = z0;
     c->last_solver3[2] = nl;
     c->last_solver3[3] = a.bctl != nullptr;  // (of the attempt that stands)
-    if (err & 1u)
-        return set_err(c, EIK_ERR_HIP, "layered solver: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", c->qtimeout_s);
-    if (err & 2u)
-        return set_err(c, EIK_ERR_NOCONVERGE, "no convergence within %llu tile visits (negative costs?)",
-                       (unsigned long long)a.qbudget);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, f->ev_start, f->ev_stop);
-    c->last = eik_stats{};
-    c->last.iterations = 1;
-    c->last.tile_visits = (int64_t)f->h_visits[0];
+    const int rc = persist3_outcome(c, err, "layered solver", "", a.qbudget, f->ev_start, f->ev_stop, f->h_visits[0]);
+    if (rc) return rc;
     c->last.inplace_passes = (int64_t)f->h_visits[1];
     c->last.fresh_visits = (int64_t)f->h_visits[2];
-    c->last.host_syncs = 1;
-    c->last.solve_ms = ms;
     // per visit: cost + T read and T write of the tile's nl layers plus the halo ring (a first
     // visit reads no T); per in-place pass: T write + halo
     // (esz: the element size above)
@@ -3009,6 +3035,26 @@ static int layered_plan(eik_ctx* c, const void* d_cost, int64_t H, int64_t W, in
         *z0 = 1;
         *nl = (int)L - 2;
     }
+    return EIK_OK;
+}
+
+// May this solve go to the layered solver: few-layer volumes (the rover's (x, y, mode) costmaps, C5), fp32
+// and fp64, in the persistent mode, whose sources' layers zlo .. zhi (the goal's z; a seed set's lowest and
+// highest) all lie among the solved ones -- a source in an all-+inf padding layer feeds its z neighbour in
+// the specification, and the layered solver never reads the padding.
+// *nl > 0: layers [*z0, *z0 + *nl) go there; *nl = 0: the general solver.
+static int layered_route(eik_ctx* c, const void* d_cost, int64_t H, int64_t W, int64_t L, int dtype, hipStream_t st,
+                         int64_t zlo, int64_t zhi, int* z0, int* nl) {
+    *z0 = 0;
+    *nl = 0;
+    const int64_t esz = dtype == EIK_F64 ? 8 : 4;
+    // (the layered kernel addresses T per tile and layer: (rows + 2) x W x L elements under 4 GiB)
+    if (c->mode != kModePersistent || c->max_rounds != 1 ||
+        (fim2dl_rows(dtype == EIK_F64) + 2) * W * L * esz >= (int64_t)UINT32_MAX)
+        return EIK_OK;
+    const int rc = layered_plan(c, d_cost, H, W, L, dtype, st, z0, nl);
+    if (rc) return rc;
+    if (zlo < *z0 || zhi >= *z0 + *nl) *nl = 0;
     return EIK_OK;
 }
 
@@ -3065,20 +3111,9 @@ static int fim3d_solve_persist(eik_ctx* c, Fim3dArgs a, int64_t B, int dtype, co
     HIPCHK(c, hipMemcpyAsync(hq, c->q3ctl.p, kQueueCtlBytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(hv, c->q3vis.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    const unsigned err = hq[192 / 4];
-    if (err & 1u)
-        return set_err(c, EIK_ERR_HIP, "3D solver: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", c->qtimeout_s);
-    if (err & 2u)
-        return set_err(c, EIK_ERR_NOCONVERGE, "3D solve: no convergence within %llu tile visits (negative costs?)",
-                       (unsigned long long)q.qbudget);
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, e0, e1);
-    c->last = eik_stats{};
-    c->last.iterations = 1;
-    c->last.host_syncs = 1;
-    c->last.tile_visits = (int64_t)hv[0];
+    const int rc = persist3_outcome(c, hq[192 / 4], "3D solver", "3D solve: ", q.qbudget, e0, e1, hv[0]);
+    if (rc) return rc;
     c->last.inplace_passes = (int64_t)hv[2];  // 3D: relaxation passes summed over the visits
-    c->last.solve_ms = ms;
     c->last.bytes_alg = (double)hv[0] * (f64 ? 8 : 4) * 3.0 * a.tx * a.ty * a.tz;
     return EIK_OK;
 }
@@ -3191,20 +3226,14 @@ static int fim3d_solve_one(eik_ctx* c, const void* d_cost, void* d_T, int64_t H,
         return set_err(c, EIK_ERR_ARG, "goal (%ld,%ld,%ld) outside %ldx%ldx%ld", (long)goal[0], (long)goal[1],
                        (long)goal[2], (long)H, (long)W, (long)L);
     HIPCHK(c, hipSetDevice(c->device));
-    // few-layer volumes (the rover's (x, y, mode) costmaps, C5): the layered solver, fp32 and fp64
-    const int64_t esz = dtype == EIK_F64 ? 8 : 4;
     // (an fp64 early-exit solve stays on fim3d.hip: its solve3_ref keeps the reference's exact ties,
     // which decide FM3D's closed set)
-    // (the layered kernel addresses T per tile and layer: (rows + 2) x W x L elements under 4 GiB)
-    if (c->mode == kModePersistent && c->max_rounds == 1 &&
-        (fim2dl_rows(dtype == EIK_F64) + 2) * W * L * esz < (int64_t)UINT32_MAX && !(stop_off >= 0 && dtype == EIK_F64)) {
-        int z0 = 0, nl = 0;
-        int rc = layered_plan(c, d_cost, H, W, L, dtype, st, &z0, &nl);
+    int z0 = 0, nl = 0;
+    if (!(stop_off >= 0 && dtype == EIK_F64)) {
+        const int rc = layered_route(c, d_cost, H, W, L, dtype, st, goal[2], goal[2], &z0, &nl);
         if (rc) return rc;
-        if (nl > 0 && goal[2] >= z0 && goal[2] < z0 + nl) {
-            return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, goal, dtype, st);
-        }
     }
+    if (nl > 0) return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, goal, dtype, st);
     return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, goal, st, stop_off);
 }
 
@@ -3224,51 +3253,79 @@ static int seeds3_check(eik_ctx* c, const char* who, int64_t H, int64_t W, int64
         if (x < 0 || y < 0 || z < 0 || x >= W || y >= H || z >= L)
             return set_err(c, EIK_ERR_ARG, "%s: seed %ld (%ld, %ld, %ld) outside %ldx%ldx%ld", who, (long)k, (long)x, (long)y,
                            (long)z, (long)H, (long)W, (long)L);
-        double v = t0 ? t0[k] : 0.0;
-        if (!(v >= 0.0) || std::isinf(v))
-            return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g (finite and >= 0 needed)", who, (long)k, v);
-        if (dtype != EIK_F64) {
-            v = (double)(float)v;
-            if (std::isinf(v)) return set_err(c, EIK_ERR_ARG, "%s: t0[%ld] = %g rounds to +inf in fp32", who, (long)k, t0[k]);
-        }
-        out[k] = Seed3Desc{x, y, z, v + 0.0};  // (+ 0.0: -0 -> +0, values order like their bits)
+        double v = 0.0;
+        const int rc = seed_t0(c, who, t0, k, dtype == EIK_F64, &v);
+        if (rc) return rc;
+        out[k] = Seed3Desc{x, y, z, v};
     }
     return EIK_OK;
 }
 
-// By default the general solver (fim3d_solve_batch: the persistent driver under 4 GiB in persistent mode,
-// else the list driver).  With EIK_OPT_SEEDS_LAYERED the few-layer volumes that fim3d_solve_one gives to the
-// layered solver go there too, by the same rule, once every seed's z lies among the solved layers: a seed in
-// an all-+inf padding layer feeds its z neighbour in the specification, and the layered solver never reads
-// the padding.
+// The seeded 3D solve from checked descriptors.  By default the general solver (fim3d_solve_batch: the
+// persistent driver under 4 GiB in persistent mode, else the list driver).  With EIK_OPT_SEEDS_LAYERED the
+// few-layer volumes that fim3d_solve_one gives to the layered solver go there too (layered_route).
+static int fim3d_solve_seeds_desc(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
+                                  const std::vector<Seed3Desc>& v, hipStream_t st) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t K = (int64_t)v.size();
+    int rc = seeds_upload(c, c->seeds3, v, st);
+    if (rc) return rc;
+    int z0 = 0, nl = 0;
+    if (c->seeds_layered) {
+        int64_t zlo = v[0].z, zhi = v[0].z;
+        for (const Seed3Desc& s : v) {
+            zlo = std::min<int64_t>(zlo, s.z);
+            zhi = std::max<int64_t>(zhi, s.z);
+        }
+        rc = layered_route(c, d_cost, H, W, L, dtype, st, zlo, zhi, &z0, &nl);
+        if (rc) return rc;
+    }
+    if (nl > 0) return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, nullptr, dtype, st, c->seeds3.d, K);
+    return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, nullptr, st, -1, c->seeds3.d, K);
+}
+
 int eik_fim3d_solve_seeds(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
                           const int64_t* seeds, const double* t0, int64_t K, void* stream) {
     if (!c) return EIK_ERR_ARG;
     const char* who = "eik_fim3d_solve_seeds";
     if (!d_cost || !d_T) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_cost ? "d_cost" : "d_T");
     std::vector<Seed3Desc> v;
-    int rc = seeds3_check(c, who, H, W, L, dtype, seeds, t0, K, v);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    rc = seeds_upload(c, c->seeds3, v, st);
-    if (rc) return rc;
-    const int64_t esz = dtype == EIK_F64 ? 8 : 4;
-    if (c->seeds_layered && c->mode == kModePersistent && c->max_rounds == 1 &&
-        (fim2dl_rows(dtype == EIK_F64) + 2) * W * L * esz < (int64_t)UINT32_MAX) {
-        int z0 = 0, nl = 0;
-        rc = layered_plan(c, d_cost, H, W, L, dtype, st, &z0, &nl);
-        if (rc) return rc;
-        bool inside = nl > 0;
-        for (int64_t k = 0; inside && k < K; ++k) inside = v[k].z >= z0 && v[k].z < z0 + nl;
-        if (inside) return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, nullptr, dtype, st, c->seeds3.d, K);
-    }
-    return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, nullptr, st, -1, c->seeds3.d, K);
+    const int rc = seeds3_check(c, who, H, W, L, dtype, seeds, t0, K, v);
+    return rc ? rc : fim3d_solve_seeds_desc(c, d_cost, d_T, H, W, L, dtype, v, (hipStream_t)stream);
 }
 
 int eik_fim3d_last_solver(const eik_ctx* c, int64_t out[4]) {
     if (!c || !out) return EIK_ERR_ARG;
     for (int i = 0; i < 4; ++i) out[i] = c->last_solver3[i];
+    return EIK_OK;
+}
+
+// the labels' cell indices are 32-bit: fewer than 2^31 cells
+// (each of H, W, L checked first: the product of three values below 2^31 / of any two cannot wrap)
+static bool labels3d_fit(int64_t H, int64_t W, int64_t L) {
+    return H < (1ll << 31) && W < (1ll << 31) && L < (1ll << 31) && H * W < (1ll << 31) && H * W * L < (1ll << 31);
+}
+
+// the labels from checked descriptors (labels3d_fit holds)
+static int labels3d_desc(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, int64_t L, const std::vector<Seed3Desc>& v,
+                         int32_t* d_label, hipStream_t st) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = H * W * L;
+    HIPCHK(c, c->lab_work.ensure(sizeof(int) * (size_t)n + sizeof(unsigned) * kLabelPasses));
+    const int rc = seeds_upload(c, c->lab_seeds3, v, st);
+    if (rc) return rc;
+    Label3Args l{};
+    l.T = d_T;
+    l.H = H;
+    l.W = W;
+    l.L = L;
+    l.n = n;
+    l.seeds = c->lab_seeds3.d;
+    l.K = (int)v.size();
+    l.par = (int*)c->lab_work.p;
+    l.label = d_label;
+    l.flags = (unsigned*)(l.par + n);
+    HIPCHK(c, labels3d(l, dtype == EIK_F64, st));
     return EIK_OK;
 }
 
@@ -3279,30 +3336,11 @@ int eik_labels3d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t 
     const char* who = "eik_labels3d_dev";
     if (!d_T || !d_label) return set_err(c, EIK_ERR_ARG, "%s: %s is NULL", who, !d_T ? "d_T" : "d_label");
     std::vector<Seed3Desc> v;
-    int rc = seeds3_check(c, who, H, W, L, dtype, seeds, t0, K, v);
+    const int rc = seeds3_check(c, who, H, W, L, dtype, seeds, t0, K, v);
     if (rc) return rc;
-    // (each of H, W, L checked first: the product of three values below 2^31 / of any two cannot wrap)
-    if (H >= (1ll << 31) || W >= (1ll << 31) || L >= (1ll << 31) || H * W >= (1ll << 31) || H * W * L >= (1ll << 31))
+    if (!labels3d_fit(H, W, L))
         return set_err(c, EIK_ERR_ARG, "%s: %ld x %ld x %ld cells (fewer than 2^31 needed)", who, (long)H, (long)W, (long)L);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t n = H * W * L;
-    HIPCHK(c, c->lab_work.ensure(sizeof(int) * (size_t)n + sizeof(unsigned) * kLabelPasses));
-    rc = seeds_upload(c, c->lab_seeds3, v, st);
-    if (rc) return rc;
-    Label3Args l{};
-    l.T = d_T;
-    l.H = H;
-    l.W = W;
-    l.L = L;
-    l.n = n;
-    l.seeds = c->lab_seeds3.d;
-    l.K = (int)K;
-    l.par = (int*)c->lab_work.p;
-    l.label = d_label;
-    l.flags = (unsigned*)(l.par + n);
-    HIPCHK(c, labels3d(l, dtype == EIK_F64, st));
-    return EIK_OK;
+    return labels3d_desc(c, d_T, dtype, H, W, L, v, d_label, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -3323,10 +3361,8 @@ static int tmap3d_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, int64_t 
     if (!c || !cost || !T || !goal) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
     const int64_t n = H * W * L;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
-    int rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    int rc = stage_inputs(c, n, cost);
+    if (!rc) rc = check_cost(c, cost, c->cost.p, n, c->stream);
     if (rc) return rc;
     const int dt = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
     rc = fim3d_solve_one(c, c->cost.p, c->T.p, H, W, L, dt, goal, c->stream, early_offset(goal, start, H, W, L));
@@ -3338,9 +3374,7 @@ static int tmap3d_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, int64_t 
         if (rc) return rc;
         src = c->T2.p;
     }
-    HIPCHK(c, dev_to_host(c, T, src, sizeof(R) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    return fetch_results(c, n, T, src);
 }
 
 // one volume from a seed set; labels (optional) from the field while it is on the device
@@ -3350,26 +3384,17 @@ static int tmap3d_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, in
     if (!c) return EIK_ERR_ARG;
     if (!cost || !T) return set_err(c, EIK_ERR_ARG, "eik_tmap3d_seeds: %s is NULL", !cost ? "cost" : "T");
     constexpr int dtype = sizeof(R) == 8 ? EIK_F64 : EIK_F32;
-    std::vector<Seed3Desc> v;  // (checked before anything is uploaded; the entry points below check again)
+    std::vector<Seed3Desc> v;  // (checked once, before anything is uploaded: the solve and the labels take the descriptors)
     int rc = seeds3_check(c, "eik_tmap3d_seeds", H, W, L, dtype, seeds, t0, K, v);
     if (rc) return rc;
-    if (labels && (H >= (1ll << 31) || W >= (1ll << 31) || L >= (1ll << 31) || H * W >= (1ll << 31) ||
-                   H * W * L >= (1ll << 31)))
-        return set_err(c, EIK_ERR_ARG, "eik_tmap3d_seeds: labels need fewer than 2^31 cells");
+    if (labels && !labels3d_fit(H, W, L)) return set_err(c, EIK_ERR_ARG, "eik_tmap3d_seeds: labels need fewer than 2^31 cells");
     const int64_t n = H * W * L;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->cost.ensure(sizeof(R) * n));
-    HIPCHK(c, c->T.ensure(sizeof(R) * n));
-    if (labels) HIPCHK(c, c->lab_out.ensure(sizeof(int32_t) * n));
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(R) * n, c->stream));
-    rc = check_cost(c, cost, c->cost.p, n, c->stream);
-    if (!rc) rc = eik_fim3d_solve_seeds(c, c->cost.p, c->T.p, H, W, L, dtype, seeds, t0, K, c->stream);
-    if (!rc && labels) rc = eik_labels3d_dev(c, c->T.p, dtype, H, W, L, seeds, t0, K, (int32_t*)c->lab_out.p, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, T, c->T.p, sizeof(R) * n, c->stream));
-    if (labels) HIPCHK(c, dev_to_host(c, labels, c->lab_out.p, sizeof(int32_t) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
+    rc = stage_inputs(c, n, cost, labels != nullptr);
+    if (!rc) rc = check_cost(c, cost, c->cost.p, n, c->stream);
+    if (!rc) rc = fim3d_solve_seeds_desc(c, c->cost.p, c->T.p, H, W, L, dtype, v, c->stream);
+    if (!rc && labels) rc = labels3d_desc(c, c->T.p, dtype, H, W, L, v, (int32_t*)c->lab_out.p, c->stream);
+    return rc ? rc : fetch_results(c, n, T, c->T.p, labels);
 }
 
 extern "C" {

@@ -6,6 +6,8 @@ Bounds are the suite's (test_gpu_fim2d.check_field): reachability masks identica
 fp64 <= 1e-9 absolute.  The new cost always goes into a SECOND tensor (two buffers in ping-pong) and no
 rectangle is given.
 """
+import functools
+
 import numpy as np
 import pytest
 
@@ -286,6 +288,53 @@ def test_seed_set_goes_through_resolve_seeds(opts, f64):
         assert np.array_equal(T[~cone].view(np.uint8), T_old[~cone].view(np.uint8))
 
     RS.run(cost, f64, opts, body)
+
+
+WIDE = (190, 370)  # 3 x 6 = 18 tiles, cut on the south and east: more than the share rule's 16-tile floor
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case():
+    """the seed set, a cost, its double (every tile changes), a one-tile edit of that, and the two new
+    costs' reference fields: made once, shared by both dtypes, left unchanged"""
+    seeds, t0 = [(20, 30), (330, 160), (180, 5)], [0.0, 12.5, 3.0]
+    cost = raster(WIDE)
+    new = 2.0 * cost
+    edit = new.copy()
+    edit[100:110, 200:210] = np.inf  # inside tile (1, 3)
+    made = cost, new, edit, seeded_reference(new, seeds, t0), seeded_reference(edit, seeds, t0)
+    for a in made:
+        a.setflags(write=False)
+    return (seeds, t0, *made)
+
+
+@pytest.mark.parametrize("f64", DTYPES)
+def test_seed_set_whole_raster_change_solves_from_scratch(f64):
+    """the share rule on a seeded solver: eik_fim2d_resolve_cost solves from scratch from the bound list"""
+    seeds, t0, cost, new, edit, R_new, R_edit = wide_case()
+
+    def body(d, c):
+        import torch
+
+        d.solve_seeds(seeds, t0)
+        c2 = torch.from_numpy(np.array(new, d.dt, order="C")).to(d.dev)
+        d.f.resolve_cost(c2.data_ptr(), d.stream)
+        T = d.T()
+        info, di = d.f.update_info(), d.f.diff_info()
+        print(f64, info, di)
+        assert di["tiles_changed"] == 18 and di["cells_raised"] == cost.size
+        assert di["solved_from_scratch"] == 1 and di["rects"] == 0 and info["fell_back"] == 0
+        check_seeded(T, R_new, seeds, t0, f64)
+        assert np.array_equal(d.labels(seeds, t0), label_rule(T, seeds, t0))
+        # ... and stays updatable: the solver is bound to c2, the first buffer takes the next cost
+        d.set_cost(edit)
+        d.f.resolve_cost(d.cd.data_ptr(), d.stream)
+        T2 = d.T()
+        di = d.f.diff_info()
+        assert di["solved_from_scratch"] == 0 and di["tiles_changed"] == 1 and d.f.update_info()["cells"] > 0
+        check_seeded(T2, R_edit, seeds, t0, f64)
+
+    RS.run(cost, f64, None, body)
 
 
 # ------------------------------------------------------------------------------- refusals

@@ -1,0 +1,123 @@
+"""The kernel launches behind the goal and seed-set entry points of csrc/eikonal_api.cpp, to compare two
+builds of libeikonal.so launch for launch (a host-side refactor must leave the sequence as it was).
+
+    EIKONAL_LIB=<a> rocprofv3 --kernel-trace --output-format csv -d A -- python tools/launch_sequence.py
+    EIKONAL_LIB=<b> rocprofv3 --kernel-trace --output-format csv -d B -- python tools/launch_sequence.py
+    python tools/launch_sequence.py --compare A B       (no GPU needed; exit status 1 when they differ)
+
+Without arguments: each entry-point family once at small sizes, through the Python API alone -- a 190 x 170
+raster (3 x 3 tiles), a 190 x 370 one (18 tiles: eik_fim2d_resolve_cost's share rule needs more than 16), a
+20 x 20 x 12 volume (the general 3D solver) and a 70 x 70 x 3 one (the layered solver).
+--compare: the kernels of both traces by start time as (name, grid, workgroup), consecutive repeats of one
+kernel collapsed (the list drivers' sweep count may vary between runs); prints the sequence and the verdict.
+Memsets and copies are not in a kernel trace.
+"""
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "planning-motion_planning_amd"))
+
+
+def calls():
+    import numpy as np
+    import torch
+    import eikonal
+    from eikonal import _lib as L
+
+    rng = np.random.default_rng(7)
+    dev = torch.device("cuda", 0)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    goal, seeds, t0 = (20, 30), [(20, 30), (150, 160), (100, 5)], [0.0, 12.5, 3.0]
+    moved = [(20, 30), (150, 160), (60, 120)]  # the third seed replaced
+    rect = [(60, 60, 71, 71)]
+    for dt, et in ((np.float32, L.EIK_F32), (np.float64, L.EIK_F64)):
+        c = eikonal.Context(0, options={"MODE": L.MODE_PERSISTENT, "QTIMEOUT": 5})
+        cost = rng.uniform(1, 10, (190, 170)).astype(dt)
+        new = cost.copy()
+        new[60:71, 60:71] = np.inf
+        up = lambda a: torch.from_numpy(a).to(dev)
+        d_cost, d_new, d_T = up(cost), up(new), torch.empty((190, 170), dtype=up(cost).dtype, device=dev)
+        f = L.Fim2d(c, 1, 190, 170, et)
+        # solve and solve_seeds; adopt + resolve; adopt_seeds + resolve_seeds; resolve_cost with a goal / seeds
+        f.solve(d_cost.data_ptr(), d_T.data_ptr(), [list(goal)], st)
+        f.adopt(d_new.data_ptr(), d_T.data_ptr(), [list(goal)], st)
+        f.resolve(rect, None, st)
+        f.solve(d_cost.data_ptr(), d_T.data_ptr(), [list(goal)], st)
+        f.resolve_cost(d_new.data_ptr(), st)
+        f.solve_seeds(d_cost.data_ptr(), d_T.data_ptr(), seeds, t0, None, st)
+        c.labels2d(d_T, seeds, t0)
+        f.adopt_seeds(d_new.data_ptr(), d_T.data_ptr(), seeds, t0, st)
+        f.resolve_seeds(rect, None, moved, t0, st)
+        f.solve_seeds(d_cost.data_ptr(), d_T.data_ptr(), seeds, t0, None, st)
+        f.resolve_cost(d_new.data_ptr(), st)
+        f.close()
+        # ... and its share rule: every one of 18 tiles changed, the solve from scratch from what is bound
+        wide = rng.uniform(1, 10, (190, 370)).astype(dt)
+        d_w, d_w2, d_Tw = up(wide), up(2 * wide), torch.empty((190, 370), dtype=d_T.dtype, device=dev)
+        g = L.Fim2d(c, 1, 190, 370, et)
+        g.solve(d_w.data_ptr(), d_Tw.data_ptr(), [list(goal)], st)
+        g.resolve_cost(d_w2.data_ptr(), st)
+        g.solve_seeds(d_w.data_ptr(), d_Tw.data_ptr(), seeds, t0, None, st)
+        g.resolve_cost(d_w2.data_ptr(), st)
+        assert g.diff_info()["solved_from_scratch"] == 1
+        g.close()
+        # the host-array forms
+        T = c.tmap2d(cost, goal, dtype=dt)
+        c.tmap2d_update(new, T, goal, rect, dtype=dt)
+        c.tmap2d_update_cost(cost, new, T, goal, dtype=dt)
+        Ts = c.tmap2d_seeds(cost, seeds, t0, dtype=dt, labels=True)[0]
+        c.tmap2d_update_seeds(new, Ts, seeds, t0, rect, seeds_new=moved, t0_new=t0, dtype=dt, labels=True)
+        c.tmap2d_update_seeds(new, Ts, seeds, t0, rect, dtype=dt)
+        # 3D: the general and the layered solver from a goal and from seeds, the labels, the list mode
+        vol, flat = rng.uniform(1, 10, (20, 20, 12)).astype(dt), rng.uniform(1, 10, (70, 70, 3)).astype(dt)
+        s3, f3 = [(3, 4, 5), (15, 16, 2)], [(10, 12, 0), (60, 50, 2)]
+        Tv = c.tmap3d(vol, (3, 4, 5), dtype=dt)
+        c.tmap3d(flat, (10, 12, 1), dtype=dt)
+        assert c.last_solver3d()["layered"] == 1
+        c.labels3d(Tv, [(3, 4, 5)])
+        for layered in (0, 1):
+            c.set_option(L.OPT_SEEDS_LAYERED, layered)
+            c.tmap3d_seeds(vol, s3, [0.0, 2.5], dtype=dt, labels=True)
+            c.tmap3d_seeds(flat, f3, [0.0, 2.5], dtype=dt, labels=True)
+            assert c.last_solver3d()["layered"] == layered
+        c.set_option(L.OPT_MODE, L.MODE_LIST)
+        c.tmap3d(vol, (3, 4, 5), dtype=dt)
+        c.close()
+    print("launch_sequence: done")
+
+
+def sequence(d):
+    rows = []
+    for fn in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
+        with open(fn, newline="") as fh:
+            for r in csv.DictReader(fh):
+                grid = "x".join(r[f"Grid_Size_{a}"] for a in "XYZ")
+                wg = "x".join(r[f"Workgroup_Size_{a}"] for a in "XYZ")
+                rows.append((int(r["Start_Timestamp"]), (r["Kernel_Name"], grid, wg)))
+    out = []
+    for _, k in sorted(rows):
+        if out and out[-1][0] == k:
+            out[-1][1] += 1
+        else:
+            out.append([k, 1])
+    return out
+
+
+def compare(a, b):
+    sa, sb = sequence(a), sequence(b)
+    for (k, n), (_, m) in zip(sa, sb):
+        print(f"{k[0][:110]}  grid {k[1]}  wg {k[2]}  x{n}" + ("" if n == m else f" / x{m}"))
+    ka, kb = [k for k, _ in sa], [k for k, _ in sb]
+    first = next((i for i, (x, y) in enumerate(zip(ka, kb)) if x != y), min(len(ka), len(kb)))
+    same = ka == kb and len(ka) > 0
+    print(f"# {a}: {sum(n for _, n in sa)} launches in {len(sa)} runs; {b}: {sum(n for _, n in sb)} in {len(sb)}")
+    print("# verdict: " + ("the two sequences are equal" if same else f"the sequences DIFFER from run {first}: "
+                           f"{ka[first] if first < len(ka) else None} / {kb[first] if first < len(kb) else None}"))
+    return 0 if same else 1
+
+
+if __name__ == "__main__":
+    sys.exit(compare(sys.argv[2], sys.argv[3]) if sys.argv[1:2] == ["--compare"] else calls())
