@@ -545,42 +545,13 @@ hipError_t cm_morph(const unsigned char* A, int64_t H, int64_t W, int r, bool er
     return hipGetLastError();
 }
 
-// ---- image_filling (:82-94) around a reachability solve ---------------------------------
-// cost for the flood fill: 1 on pixels equal to the seed value m[0], +inf elsewhere
-// Reachability by the block-FIM solver: cost 0 on the seed's value (+inf elsewhere), so a reached
-// cell is 0 at once and never revisited for a refinement -- only connectivity is asked.  (The solve
-// still takes ~2.3 ms at 4096^2, as with cost 1: a flood from the corner pixel is a chain of ~128
-// tile hops across the raster, tools/rover_probe.py under rocprofv3.)
-__global__ void cm_fill_cost_kernel(const unsigned char* __restrict__ m, int64_t n, float* __restrict__ c) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    c[i] = m[i] == m[0] ? 0.f : __builtin_inff();
-}
-// filled = seed pixel's component set to 1; out = m | (~filled - 254) (uint8): seed 0 -> holes
-// (zeros not reached) become 1; seed 1 -> every pixel 1 (the reference's arithmetic)
-__global__ void cm_fill_apply_kernel(unsigned char* __restrict__ m, const float* __restrict__ T, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const unsigned char seed = m[0];  // read before any write: m[0] is never changed by this kernel
-    const unsigned char filled = (m[i] == seed && T[i] != __builtin_inff()) ? 1 : m[i];
-    const unsigned char inv = (unsigned char)((unsigned char)~filled - 254);
-    m[i] = m[i] | inv;
-}
-
-hipError_t cm_fill_cost(const unsigned char* m, int64_t n, float* c, hipStream_t st) {
-    hipLaunchKernelGGL(cm_fill_cost_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m, n, c);
-    return hipGetLastError();
-}
-hipError_t cm_fill_apply(unsigned char* m, const float* T, int64_t n, hipStream_t st) {
-    hipLaunchKernelGGL(cm_fill_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, m, T, n);
-    return hipGetLastError();
-}
-
 // ---- image_filling (:82-94) as connected components: the 4-connected component of pixel (0, 0)
 // among the pixels equal to m[0], by lock-free union-find (links always from the larger to the
-// smaller index, so the component of pixel 0 has root 0).  The block-FIM flood (cm_fill_cost /
-// cm_fill_apply above) is a chain of ~128 tile hops from the corner across a 4096^2 raster
-// (2.3 ms); here no information travels tile by tile:
+// smaller index, so the component of pixel 0 has root 0).  The flood this replaced (removed: cm_fill_cost
+// wrote cost 0 on the seed's value and +inf elsewhere, the block-FIM solver ran on it, cm_fill_apply filled
+// what it reached) took ~2.3 ms at 4096^2 whatever the cost: a flood from the corner pixel is a chain of
+// ~128 tile hops across the raster (tools/rover_probe.py under rocprofv3).  Here no information travels
+// tile by tile:
 //  1. per 32 x 32 tile, union-find in LDS over the tile's pixels, each pixel's local root written
 //     as a global index (lroot; -1: not the seed value);
 //  2. one thread per pixel pair across a tile border: union of their local roots in `parent`;
@@ -688,7 +659,8 @@ __global__ void cm_ccl_resolve_kernel(int64_t n, const int* __restrict__ lroot, 
     parent[i] = ccl_find(parent, (int)i, 1);
 }
 
-// the fill of cm_fill_apply_kernel with "reached" = in pixel 0's component
+// filled = seed pixel's component ("reached" = in pixel 0's component) set to 1; out = m | (~filled - 254)
+// (uint8): seed 0 -> holes (zeros not reached) become 1; seed 1 -> every pixel 1 (the reference's arithmetic)
 __global__ void cm_ccl_apply_kernel(unsigned char* __restrict__ m, const int* __restrict__ lroot,
                                     const int* __restrict__ parent, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -340,9 +340,7 @@ hipError_t cm_morph(const unsigned char* A, int64_t H, int64_t W, int r, bool er
 hipError_t cm_edt_ramp(const unsigned char* m, int64_t H, int64_t W, int r, int* g, int* D, int* vbuf, hipStream_t st);
 hipError_t cm_edt(const unsigned char* m, unsigned char val, int64_t H, int64_t W, int* g, int* D, int* vbuf,
                   hipStream_t st);
-hipError_t cm_fill_cost(const unsigned char* m, int64_t n, float* c, hipStream_t st);
-hipError_t cm_fill_apply(unsigned char* m, const float* T, int64_t n, hipStream_t st);
-// the same fill by connected components (union-find; lroot, parent: n ints of scratch)
+// image_filling (:82-94) by connected components (union-find; lroot, parent: n ints of scratch)
 hipError_t cm_fill_ccl(unsigned char* m, int64_t H, int64_t W, int* lroot, int* parent, hipStream_t st);
 // first index with cost < 0 or NaN into *first (~0: none); costmap.hip
 hipError_t cost_check(const void* cost, int64_t n, bool f64, unsigned long long* first, hipStream_t st);

@@ -17,36 +17,13 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/eikonal.h"
-#include "eik_common.hpp"
-#include "eik_kernels.hpp"
+#include "api_internal.hpp"
 
 using namespace eik;
 
-int rover_assemble(const double* pathS, int64_t nS, const double* pathG, int64_t nG, const double* Z, int64_t H,
-                   int64_t W, const eik_rover_query* q, double* path_xyz, double* heading, int64_t cap, int64_t* n_out,
-                   double zmin_known);  // rover.cpp
+namespace eik_api __attribute__((visibility("hidden"))) {
 
-namespace {
-
-thread_local std::string g_create_err;
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= bytes) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-        hipError_t e = hipMalloc(&p, n);
-        if (e == hipSuccess) bytes = n;
-        return e;
-    }
-    ~DevBuf() {
-        if (p) (void)hipFree(p);
-    }
-};
+static thread_local std::string g_create_err;
 
 // Host memcpy split over a few worker threads and the caller (the pinned-staging copies below).
 // ONE pool per process, shared by every context (8 DD ranks sharing a node each started
@@ -121,182 +98,6 @@ class CopyPool {
     bool quit_ = false;
 };
 
-// Descriptors of one batched path call (eik_path*_batch_dev): a pinned host block and its device
-// twin.  The call fills h, copies it to d on the caller's stream, launches, and records ev; the
-// block is free again once ev has completed (stage_desc).
-struct DescBlock {
-    GdmDesc* h = nullptr;
-    GdmDesc* d = nullptr;
-    int64_t cap = 0;
-    hipEvent_t ev = nullptr;
-};
-
-// The seeds of one multi-source call (eik_fim2d_start_seeds, eik_labels2d_dev), or the root entries of one
-// seeded update (eik_fim2d_update_seeds): a pinned host block and its device twin, grown on demand; ev
-// marks the block's last upload (waited for before reuse).
-template <typename D>
-struct Stage {
-    D* h = nullptr;
-    D* d = nullptr;
-    int64_t cap = 0;
-    hipEvent_t ev = nullptr;
-    void release() {
-        if (h) (void)hipHostFree(h);
-        if (d) (void)hipFree(d);
-        if (ev) (void)hipEventDestroy(ev);
-        h = d = nullptr;
-        ev = nullptr;
-        cap = 0;
-    }
-};
-
-using SeedStage = Stage<SeedDesc>;
-using RootStage = Stage<RootDesc>;
-using Seed3Stage = Stage<Seed3Desc>;
-
-}  // namespace
-
-constexpr double kFrontsMargin = 1.25;  // capped bidirectional fronts (solve_fronts)
-
-struct eik_ctx {
-    int device = 0;
-    int cu_count = 256;
-    hipStream_t stream = nullptr;
-    std::string err;
-    int max_rounds = 1;
-    double tol = 0.0;
-    double delta = 0.0;  // 0: unordered FIM
-    int sync_every = 8;
-    int mode = kModePersistent;  // EIK_OPT_MODE
-    double qtimeout_s = 30.0;    // EIK_OPT_QTIMEOUT: persistent-mode spin limit
-    unsigned long long max_visits = 0;  // EIK_OPT_MAX_VISITS (0: per-solver default)
-    int passes = 0;              // EIK_OPT_PASSES: in-place passes per persistent visit (0: adaptive)
-    bool fresh_first = false;    // EIK_OPT_FRESH_FIRST: fresh tiles jump a backlogged FIFO
-    int sched = 1;               // EIK_OPT_SCHED: in-place scheduling of persistent visits
-    int live_pack = 0;           // EIK_OPT_LIVE_PACK: the halo agent packs only idle tiles' edges
-    // EIK_OPT_PRIO: the priority bands' width in units of 64 x the cost's geometric mean (0: the
-    // plain FIFO; < 0, the default: default_prio() in fp64, on the layered solver and on one fp32 2D map of
-    // >= kWideTiles tiles, else 0 in fp32 2D;
-    // round 5's first default was 1 in fp64).  fp64 at 1: C2 2.44-2.50 -> 2.37 ms, C4 at
-    // one GPU 10.5 -> 13.8 Gcells/s; 0.5 / 2 lose on C4 (6.9 / 12.9; profiles/r05i_prio_ab.log).  fp32
-    // solves are twice as fast per pass and the one-dispatcher bands held them back: C2 fp32 1.6 ->
-    // 1.9 ms, C4 fp32 18.7 -> 10.8 Gcells/s (profiles/r05j_bench.json) -- until the 128-entry dispatches of
-    // round 6 (C4 fp32 with bands 18.4 -> 19.5).  Batches of > 2 maps: FIFO.
-    // The layered solver's bands (both dtypes, default_prio()): C5 fp64 1.92 -> 3.65, fp32 4.73 -> 6.2
-    // Gcells/s (profiles/r05ac_layered_prio_ab.log, r05ad_prio_width_ab.log).
-    double prio = -1.0;
-    int prio_ring = 0;           // EIK_OPT_PRIO_RING: slots per priority band (0: pow2 >= 2 x the tiles)
-    int prio_dispatch = 0;       // EIK_OPT_PRIO_DISPATCH: band entries per dispatch (0: 128 on maps of >= kWideTiles, else 16)
-    int wide = -1;               // EIK_OPT_WIDE: the fp32 2D persistent kernel's form (< 0: by size, wide_form())
-    int64_t last_form[4] = {};   // eik_last_form: wide form launched, bands set up, pass cap, dispatch batch
-    // EIK_OPT_LAYER_PLANAR (default 1): the layered solver works on layer-planar copies.  C5 kernel
-    // traffic per launch 9.06 -> 3.92 GB (fp32), 20.3 -> 8.6 GB (fp64), the time within noise
-    // (the layered sweep is VALU-bound; profiles/r05c_pmc_traffic_c5*.json, r05h_prio_planar_ab.log)
-    int layer_planar = 1;
-    int seeds_layered = 0;       // EIK_OPT_SEEDS_LAYERED: eik_fim3d_solve_seeds routes as eik_fim3d_solve does
-    int64_t last_solver3[4] = {};  // eik_fim3d_last_solver: layered solver ran, z0, nl, bands set up
-    DevBuf lp_cost, lp_T;        // those copies (solve_layered)
-    int path_loop = 4;           // EIK_OPT_PATH_LOOP: 2D walker loop form (4: lane pairs, round 5,
-                                 // 0.405 -> 0.30 us/step on the bench path, profiles/r05k_walker_ab.log)
-    int timing = 0;
-    int grid = 0;
-    eik_stats last{};
-    eik_fim2d* cached = nullptr;  // solver reused by the host-buffer entry points
-    eik_fim2d* cached_l = nullptr;  // queue state of the layered 3D solver (fim2dl.hip), fp32 tiles
-    eik_fim2d* cached_l64 = nullptr;  // the same for the fp64 layered solver's 40-row tiles
-    eik_fim2d* cached_fill = nullptr;  // reachability solver of the cost builder's hole filling
-    eik_fim2d* cached_fronts = nullptr;  // coarse B = 2 solver of the capped bidirectional fronts
-    double fronts_cap = 1.25;          // EIK_OPT_FRONTS_CAP: cap margin (0: full fronts)
-    DevBuf fronts;                     // capped fronts: coarse cost (2 maps) | coarse T (2 maps) | FrontsCheck
-    int64_t fronts_info[10] = {};      // eik_fronts_info: capped, fallback, kept G / S, members G / S,
-                                       // band cells G / S, band relaxation sweeps G / S
-    bool exact_band = false;           // EIK_OPT_EXACT_BAND: replay the reference's band (bidir_exact.hip)
-    DevBuf exact;                      // its scratch: events, ranks, sort keys
-    unsigned long long exact_info[5] = {};  // eik_exact_info: passes, sweeps G / S, tie launches, microseconds
-    DevBuf cm_u8, cm_i32, cm_f32, cm_f64;  // cost-builder scratch
-    DevBuf arm;                            // end-effector volume scratch (arm.hip)
-    int resident_l[2][5] = {};  // co-resident workgroups of fim2dl_persist_kernel<R, nl> (f32, f64)
-    DevBuf cost, T, T2, goals, work, misc;
-    DevBuf l3, c3, m3, v3;             // 3D solver scratch (lists, counts, marks, visits)
-    int max_passes3 = 24;
-    int* h3 = nullptr;                 // 3D solver: pinned count + visits words (made once)
-    DevBuf q3ctl, q3slot, q3state, q3vis;  // 3D persistent driver: tile FIFO (fim_engine.hpp)
-    unsigned* h_q3 = nullptr;          // pinned copy of q3ctl + the two visit counters
-    int resident3[2] = {0, 0};         // co-resident workgroups of fim3d_persist_kernel (f32, f64)
-    hipStream_t stream2 = nullptr;     // second stream: the rover path's two walks run side by side
-    // pinned staging of large host <-> device copies (host_to_dev / dev_to_host)
-    char* stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    CopyPool* pool = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t e3[2] = {nullptr, nullptr};
-    // the cost diff (cost_diff.hip): every tile's record, the totals + the changed tiles'
-    // list, the list's pinned copy (1 + max(kMaxRects, tiles) records) and the kernels' timing events
-    DevBuf diff_rec, diff_out, cost2;  // (cost2: the host entries' old cost)
-    DiffRecord* h_diff = nullptr;
-    int64_t h_diff_cap = 0;
-    hipEvent_t ev_diff[2] = {nullptr, nullptr};
-    // EIK_OPT_DIFF_LOADS: non-temporal loads by default -- 16384^2 fp64 0.75-0.77 -> 0.66-0.71 ms, 4096^2 fp64
-    // 0.057-0.066 -> 0.049-0.062 ms, fp32 equal (profiles/cost_diff_ab.log)
-    bool diff_nt = true;
-    double diff_share = -1.0;          // EIK_OPT_DIFF_SHARE (< 0: kDiffFullShare)
-    SeedStage lab_seeds;               // eik_labels2d_dev: its seeds, and its scratch (parents | pass flags)
-    DevBuf lab_work, lab_out;          // (lab_out: the host entries' device labels)
-    Seed3Stage seeds3, lab_seeds3;     // eik_fim3d_solve_seeds / eik_labels3d_dev: their seeds (scratch: lab_work)
-    std::vector<DescBlock> desc;       // batched paths: descriptor blocks in flight or free (stage_desc)
-    size_t desc_next = 0;
-};
-
-struct eik_fim2d {
-    eik_ctx* ctx = nullptr;
-    int64_t B = 0, H = 0, W = 0;
-    bool f64 = false;
-    Fim2dArgs a{};
-    hipStream_t stream = nullptr;
-    DevBuf lists, counts, mark, edge, goals, key;
-    DevBuf ecol;                         // every tile's two edge columns (Fim2dArgs::ecol)
-    DevBuf qctl, qslot, qstate;          // persistent-mode FIFO
-    DevBuf bslot, bctl;                  // priority bands (EIK_OPT_PRIO)
-    int* h_counts = nullptr;             // pinned
-    unsigned* h_q = nullptr;             // pinned copy of qctl
-    unsigned long long* h_visits = nullptr;
-    int64_t* h_goals = nullptr;          // pinned: the goals' upload does not stall the host
-    int64_t iterations = 0, host_syncs = 0, max_iters = 0;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    std::vector<hipEvent_t> ev_pool;     // per-launch timing pairs (timing option)
-    size_t ev_used = 0;
-    double sweep_ms = 0.0, solve_ms = 0.0;
-    bool started = false;
-    bool defer_sync = false;             // eik_fim2d_solve: the launch's read-back syncs with the finish
-    bool need_rewind = false;            // a launch without its queue rewind ran since the last init
-    bool band_overflow = false;          // the last launch stopped on a full priority band (qerror bit 4)
-    bool no_bands = false;               // ... so this solver's next starts use the FIFO
-    // a seed set started the bound solve (eik_fim2d_start_seeds): eik_fim2d_update knows one goal only,
-    // eik_fim2d_update_seeds re-solves it
-    bool seeded = false;
-    SeedStage sd;                        // its seeds
-    std::vector<SeedDesc> bound;         // the bound seed list (host copy: start_seeds, adopt_seeds, update_seeds)
-    RootStage roots;                     // eik_fim2d_update_seeds: the old list's cells (seed_diff.hpp)
-    int64_t last_active = -1;            // tiles left by the last persistent launch read back (-1: none yet, or it failed)
-    // incremental re-solve (replan.hip): descriptors (pinned + device), recorded tiles, counters
-    DevBuf rp_rects, rp_list, rp_flag, rp_info;
-    ReplanRect* h_rects = nullptr;       // pinned [kMaxRects]
-    unsigned long long* h_info = nullptr;  // pinned [6]
-    hipEvent_t ev_rp[2] = {nullptr, nullptr};
-    bool rp_timed = false, rp_fallback = false;  // events recorded; the last resolve ended in a full solve
-    int flood_grid = 0;                  // co-resident workgroups of the flood kernel
-    int persist_grid = 0;                // co-resident workgroups of the persistent kernel
-    int64_t diff_info[8] = {};           // eik_fim2d_diff_info: of the last eik_fim2d_resolve_cost
-    bool persist_wide = false;           // ... of which form (EIK_OPT_WIDE can change it between solves)
-    // live domain decomposition: hold word on the device, mailbox of the halo agent on the host
-    DevBuf hold;
-    LiveBox* box = nullptr;              // pinned, coherent
-    bool live_on = false;
-    // a layered volume's block (eik_fim3dl_create: the layered solver, fim2dl.hip): nl > 0
-    int lnl = 0, lz0 = 0;
-    int64_t lL = 1;
-};
-
 // The fp32 2D persistent kernel's form: the 4-waves-per-SIMD one on one large raster (a batch of
 // small maps: no gain), or as EIK_OPT_WIDE says.  fp64 has the one form.
 static bool wide_form(const eik_fim2d* f) {
@@ -313,7 +114,7 @@ static int persist_resident(eik_fim2d* f, bool wide) {
     return f->persist_grid;
 }
 
-static int set_err(eik_ctx* c, int code, const char* fmt, ...) {
+int set_err(eik_ctx* c, int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -325,14 +126,6 @@ static int set_err(eik_ctx* c, int code, const char* fmt, ...) {
         g_create_err = buf;
     return code;
 }
-
-#define HIPCHK(ctx, expr)                                                                          \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return set_err((ctx), e_ == hipErrorOutOfMemory ? EIK_ERR_NOMEM : EIK_ERR_HIP, "%s: %s (%s:%d)", \
-                           #expr, hipGetErrorString(e_), __FILE__, __LINE__);                      \
-    } while (0)
 
 static int bytes_per_visit(bool f64) { return (f64 ? 8 : 4) * (3 * kTile * kTile + 4 * kTile); }
 // in-place pass of a busy tile (persistent mode): T write-back + halo ring re-read
@@ -347,7 +140,6 @@ static int bytes_per_pass(bool f64) { return (f64 ? 8 : 4) * (kTile * kTile + 4 
 // work).  A buffer wholly inside a pinned block (eik_host_alloc) goes as ONE hipMemcpyAsync on st
 // and both return at once: the source must stay unchanged, and dst is valid, only after st is
 // synchronised -- every caller synchronises st before it returns to its own caller.
-constexpr size_t kStageChunk = 8ull << 20;
 // pinned host blocks handed out by eik_host_alloc: a copy wholly inside one goes as one DMA
 static std::mutex g_pin_mu;
 static std::vector<std::pair<uintptr_t, size_t>> g_pinned;
@@ -372,7 +164,7 @@ static hipError_t stage_init(eik_ctx* c) {
     if (!c->pool) c->pool = CopyPool::shared();
     return hipSuccess;
 }
-static hipError_t host_to_dev(eik_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
+hipError_t host_to_dev(eik_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
     if (bytes < 2 * kStageChunk || is_pinned(src, bytes)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st);
     hipError_t e = stage_init(c);
     if (e != hipSuccess) return e;
@@ -388,7 +180,7 @@ static hipError_t host_to_dev(eik_ctx* c, void* dst, const void* src, size_t byt
     }
     return hipSuccess;
 }
-static hipError_t dev_to_host(eik_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
+hipError_t dev_to_host(eik_ctx* c, void* dst, const void* src, size_t bytes, hipStream_t st) {
     if (bytes < 2 * kStageChunk || is_pinned(dst, bytes)) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
     hipError_t e = stage_init(c);
     if (e != hipSuccess) return e;
@@ -436,6 +228,8 @@ static int seeds_upload(eik_ctx* c, Stage<D>& s, const std::vector<D>& v, hipStr
     return EIK_OK;
 }
 
+}  // namespace eik_api
+
 extern "C" {
 
 const char* eik_version(void) { return "eikonal-mi355x 0.1 (gfx950 block-FIM, 64x64 tiles)"; }
@@ -469,7 +263,6 @@ void eik_destroy(eik_ctx* c) {
     if (c->cached) eik_fim2d_destroy(c->cached);
     if (c->cached_l) eik_fim2d_destroy(c->cached_l);
     if (c->cached_l64) eik_fim2d_destroy(c->cached_l64);
-    if (c->cached_fill) eik_fim2d_destroy(c->cached_fill);
     if (c->cached_fronts) eik_fim2d_destroy(c->cached_fronts);
     if (c->h3) (void)hipHostFree(c->h3);
     if (c->h_q3) (void)hipHostFree(c->h_q3);
@@ -663,6 +456,25 @@ static int fim2d_create_rows(eik_ctx* c, int64_t B, int64_t H, int64_t W, int dt
     // safety cap: a monotone solve visits each tile a bounded number of times; negative costs
     // (invalid input on a device buffer) would otherwise iterate forever.
     f->max_iters = 64 * (ntx + nty) + 8 * tiles / B + 4096;
+    *out = f;
+    return EIK_OK;
+}
+
+// The solver cached in `slot`, reused when it is one of B maps of H x W cells of this dtype, else remade in
+// tiles of th rows.  Every slot compares what the host entries' slot always did: the layered slots are per
+// dtype and the coarse fronts' solver is always B = 2 fp64, so for them only H and W ever differ.  Destroy,
+// clear the slot, then create: a failed create leaves the slot empty.
+static int cached_solver(eik_ctx* c, eik_fim2d*& slot, int64_t B, int64_t H, int64_t W, int dtype, int th, eik_fim2d** out) {
+    eik_fim2d* f = slot;
+    if (f && f->B == B && f->H == H && f->W == W && (int)f->f64 == (dtype == EIK_F64)) {
+        *out = f;
+        return EIK_OK;
+    }
+    if (f) eik_fim2d_destroy(f);
+    slot = nullptr;
+    int rc = fim2d_create_rows(c, B, H, W, dtype, th, &f);
+    if (rc) return rc;
+    slot = f;
     *out = f;
     return EIK_OK;
 }
@@ -898,7 +710,7 @@ int eik_fim2d_start_seeds(eik_fim2d* f, const void* d_cost, void* d_T, const int
 // the persistent launch's queue words (h_q, read back after it): errors and the active count
 static int persist_result(eik_fim2d* f, int64_t* active) {
     eik_ctx* c = f->ctx;
-    const unsigned err = f->h_q[192 / 4];
+    const unsigned err = f->h_q[kQErrorWord];
     f->band_overflow = (err & 4u) != 0u;
     if (f->band_overflow)
         return set_err(c, EIK_ERR_HIP, "persistent solver: a priority band's ring is full (EIK_OPT_PRIO=0 "
@@ -909,8 +721,8 @@ static int persist_result(eik_fim2d* f, int64_t* active) {
     if (err & 2u)
         return set_err(c, EIK_ERR_NOCONVERGE, "no convergence within %llu tile visits (negative costs?)",
                        (unsigned long long)f->a.qbudget);
-    f->last_active = f->h_q[128 / 4];
-    if (active) *active = f->h_q[128 / 4];
+    f->last_active = f->h_q[kQActiveWord];
+    if (active) *active = f->h_q[kQActiveWord];
     return EIK_OK;
 }
 
@@ -1090,7 +902,7 @@ int eik_fim2d_active(eik_fim2d* f, int64_t* active) {
     if (f->a.mode == kModePersistent) {
         HIPCHK(c, hipMemcpyAsync(f->h_q, f->qctl.p, kQueueCtlBytes, hipMemcpyDeviceToHost, f->stream));
         HIPCHK(c, hipStreamSynchronize(f->stream));
-        *active = f->h_q[128 / 4];
+        *active = f->h_q[kQActiveWord];
         return EIK_OK;
     }
     HIPCHK(c, hipMemcpyAsync(f->h_counts, (int*)f->counts.p + (f->iterations % 3), sizeof(int), hipMemcpyDeviceToHost,
@@ -1791,6 +1603,20 @@ int eik_fim2d_live_bind(eik_fim2d* f, void* const send[8], void* const recv[8]) 
     return EIK_OK;
 }
 
+// a live launch's queue error bits (the halo agent's copy in the mailbox, the queue's own word after the release)
+static int live_queue_error(eik_fim2d* f, unsigned err) {
+    eik_ctx* c = f->ctx;
+    if (err & 4u)
+        return set_err(c, EIK_ERR_HIP, "live solve: a priority band's ring is full (EIK_OPT_PRIO=0 or a larger "
+                                       "EIK_OPT_PRIO_RING)");
+    if (err & 1u)
+        return set_err(c, EIK_ERR_HIP, "live solve: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", c->qtimeout_s);
+    if (err & 2u)
+        return set_err(c, EIK_ERR_NOCONVERGE, "no convergence within %llu tile visits (negative costs?)",
+                       (unsigned long long)f->a.qbudget);
+    return EIK_OK;
+}
+
 // post one command to the halo agent and wait for it (bounded by the queue timeout)
 static int live_cmd(eik_fim2d* f, unsigned op, unsigned par) {
     eik_ctx* c = f->ctx;
@@ -1826,22 +1652,13 @@ static int live_cmd(eik_fim2d* f, unsigned op, unsigned par) {
                 return set_err(c, EIK_ERR_HIP,
                                "live solve: the persistent launch is no longer running (queue error %u, active %d, "
                                "visits %llu, passes %llu, fifo head-tail %lld, fullest band %lld of %u slots)",
-                               q[192 / 4], (int)q[128 / 4], vis[0], vis[1], (long long)(qh - qt), band_max,
+                               q[kQErrorWord], (int)q[kQActiveWord], vis[0], vis[1], (long long)(qh - qt), band_max,
                                f->a.bctl ? f->a.bmask + 1u : 0u);
             }
         }
         __builtin_ia32_pause();
     }
-    const unsigned err = __atomic_load_n(&b->error, __ATOMIC_RELAXED);
-    if (err & 4u)
-        return set_err(c, EIK_ERR_HIP, "live solve: a priority band's ring is full (EIK_OPT_PRIO=0 or a larger "
-                                       "EIK_OPT_PRIO_RING)");
-    if (err & 1u)
-        return set_err(c, EIK_ERR_HIP, "live solve: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", c->qtimeout_s);
-    if (err & 2u)
-        return set_err(c, EIK_ERR_NOCONVERGE, "no convergence within %llu tile visits (negative costs?)",
-                       (unsigned long long)f->a.qbudget);
-    return EIK_OK;
+    return live_queue_error(f, __atomic_load_n(&b->error, __ATOMIC_RELAXED));
 }
 
 int eik_fim2d_launch(eik_fim2d* f, int live) {
@@ -1936,16 +1753,9 @@ int eik_fim2d_release(eik_fim2d* f, int64_t* active) {
     ++f->host_syncs;
     if (c->timing) drain_timing(f);
     if (rc_cmd) return rc_cmd;
-    const unsigned err = f->h_q[192 / 4];
-    if (err & 4u)
-        return set_err(c, EIK_ERR_HIP, "live solve: a priority band's ring is full (EIK_OPT_PRIO=0 or a larger "
-                                       "EIK_OPT_PRIO_RING)");
-    if (err & 1u)
-        return set_err(c, EIK_ERR_HIP, "live solve: a queue wait exceeded %.1f s (EIK_OPT_QTIMEOUT)", c->qtimeout_s);
-    if (err & 2u)
-        return set_err(c, EIK_ERR_NOCONVERGE, "no convergence within %llu tile visits (negative costs?)",
-                       (unsigned long long)f->a.qbudget);
-    if (active) *active = f->h_q[128 / 4];
+    const int rc = live_queue_error(f, f->h_q[kQErrorWord]);
+    if (rc) return rc;
+    if (active) *active = f->h_q[kQActiveWord];
     return EIK_OK;
 }
 
@@ -2042,36 +1852,11 @@ static void fill_stats(const eik_fim2d* f, eik_stats* out) {
 
 }  // extern "C"
 
-// ------------------------------------------------------------------- host-buffer drop-ins
-static int get_solver(eik_ctx* c, int64_t B, int64_t H, int64_t W, int dtype, eik_fim2d** out) {
-    eik_fim2d* f = c->cached;
-    if (f && f->B == B && f->H == H && f->W == W && (int)f->f64 == (dtype == EIK_F64)) {
-        *out = f;
-        return EIK_OK;
-    }
-    if (f) eik_fim2d_destroy(f);
-    c->cached = nullptr;
-    int rc = eik_fim2d_create(c, B, H, W, dtype, &f);
-    if (rc) return rc;
-    c->cached = f;
-    *out = f;
-    return EIK_OK;
-}
+namespace eik_api __attribute__((visibility("hidden"))) {
 
-// Costs must be >= 0 or +inf (negative or NaN: EIK_ERR_ARG).  Checked on the device copy `dev`
-// of the host array `cost` (a host scan of a 4096^2 f64 raster took ~19 ms at one core's memory
-// bandwidth): one short kernel and an 8-byte read-back, before anything is solved.
-template <typename R>
-static int check_cost(eik_ctx* c, const R* cost, const void* dev, int64_t n, hipStream_t st) {
-    HIPCHK(c, c->misc.ensure(64));
-    unsigned long long* first = (unsigned long long*)c->misc.p + 7;  // (words 0..: the join's)
-    HIPCHK(c, cost_check(dev, n, sizeof(R) == 8, first, st));
-    unsigned long long i = 0;
-    HIPCHK(c, hipMemcpyAsync(&i, first, sizeof i, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (i != ~0ull)
-        return set_err(c, EIK_ERR_ARG, "cost[%ld] = %g: costs must be >= 0 or +inf", (long)i, (double)cost[i]);
-    return EIK_OK;
+// ------------------------------------------------------------------- host-buffer drop-ins
+int get_solver(eik_ctx* c, int64_t B, int64_t H, int64_t W, int dtype, eik_fim2d** out) {
+    return cached_solver(c, c->cached, B, H, W, dtype, kTile, out);
 }
 
 // The host entries' inputs of n cells on the device, in stream order: cost_old (optional) in c->cost2, cost in
@@ -2218,6 +2003,156 @@ static int tmap_update_seeds_host(eik_ctx* c, const R* cost, R* T, int64_t H, in
     return rc ? rc : fetch_results(c, n, T, c->T.p, labels);
 }
 
+// nodeJoin + partial fields from the two device-resident full fields dT[0:n] (goal front) and
+// dT[n:2n] (start front), in place; *best = the packed join (~0: the fronts never meet).  d_cost
+// (the fronts' raster): band cells by the band relaxation (bidir.hip), else at their full-field
+// values; d_chk: the capped fronts' check.  Ends with the stream synchronised on *best.
+// src (with d_cost): the goal's and the start's linear index, for EIK_OPT_EXACT_BAND's replay.
+static int join_and_partial(eik_ctx* c, double* dT, int64_t n, int64_t H, int64_t W, unsigned long long* best,
+                            int64_t members[2], const double* d_cost = nullptr, FrontsCheck* d_chk = nullptr,
+                            FrontsCheck* h_chk = nullptr, const int64_t* src = nullptr) {
+    hipStream_t st = c->stream;
+    HIPCHK(c, c->work.ensure(bidir_join_work_bytes(n)));
+    HIPCHK(c, c->misc.ensure(64));
+    HIPCHK(c, bidir_join(dT, dT + n, n, c->work.p, c->work.bytes, (unsigned long long*)c->misc.p, st, members));
+    if (d_cost && src && c->exact_band && members[0] > 0 && members[1] > 0) {
+        // the reference's own band values, LIFO ties and nodeJoin, replayed from the join's ranks
+        const unsigned *rg = nullptr, *rs = nullptr;
+        bidir_join_ranks(c->work.p, n, &rg, &rs);
+        HIPCHK(c, c->exact.ensure(bidir_exact_work_bytes(n, members[0], members[1])));
+        EventPair ev;  // (destroyed on every return path)
+        hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
+        HIPCHK(c, hipEventCreate(&e0));
+        HIPCHK(c, hipEventCreate(&e1));
+        HIPCHK(c, hipEventRecord(e0, st));
+        unsigned long long info[4] = {0, 0, 0, 0};
+        const hipError_t e = bidir_exact(dT, dT + n, d_cost, H, W, src[0], src[1], rg, rs, members, c->exact.p,
+                                         c->exact.bytes, (unsigned long long*)c->misc.p, st, info);
+        if (e == hipErrorNotReady || e == hipErrorNotSupported || e == hipErrorIllegalState)
+            return set_err(c, EIK_ERR_NOCONVERGE,
+                           e == hipErrorNotReady      ? "biComputeTmap: the exact band replay did not settle"
+                           : e == hipErrorNotSupported ? "biComputeTmap: the exact band replay met a run of more than "
+                                                         "4096 cells of exactly equal T (a zero-cost region)"
+                                                       : "biComputeTmap: the exact meeting is not clear of the ranked "
+                                                         "cells' bound");
+        HIPCHK(c, e);
+        HIPCHK(c, hipEventRecord(e1, st));
+        HIPCHK(c, hipMemcpyAsync(best, c->misc.p, sizeof *best, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        for (int q = 0; q < 4; ++q) c->exact_info[q] = info[q];
+        c->exact_info[4] = (unsigned long long)(ms * 1000.0f);
+        for (int q = 0; q < 4; ++q) c->fronts_info[6 + q] = 0;
+        if (d_chk) {
+            HIPCHK(c, hipMemcpyAsync(h_chk, d_chk, sizeof *h_chk, hipMemcpyDeviceToHost, st));
+            HIPCHK(c, hipStreamSynchronize(st));
+            h_chk->viol = 0;  // band values come from the replay's events, not from the capped field
+        }
+        return EIK_OK;
+    }
+    {
+        const hipError_t e = bidir_partial(dT, dT + n, H, W, c->work.p, (const unsigned long long*)c->misc.p, st, d_cost,
+                                           d_chk ? &d_chk->viol : nullptr);
+        if (e == hipErrorNotReady)
+            return set_err(c, EIK_ERR_NOCONVERGE, "biComputeTmap: the band relaxation of the partial fields did not settle");
+        HIPCHK(c, e);
+    }
+    if (d_cost) {
+        unsigned bs[4] = {0, 0, 0, 0};
+        HIPCHK(c, bidir_band_stats(c->work.p, n, bs, st));
+        for (int q = 0; q < 4; ++q) c->fronts_info[6 + q] = bs[q];
+    }
+    HIPCHK(c, hipMemcpyAsync(best, c->misc.p, sizeof *best, hipMemcpyDeviceToHost, st));
+    if (d_chk) HIPCHK(c, hipMemcpyAsync(h_chk, d_chk, sizeof *h_chk, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    return EIK_OK;
+}
+
+// Capped fronts: rasters of at least kFrontsCapCells cells, F x F coarse blocks with F =
+// max(4, ceil(max(H, W) / 512)), cap = F x (coarse T at the join bound's rank K0, bidir.hip
+// fronts_estimate) x margin (kFrontsMargin, EIK_OPT_FRONTS_CAP) + the largest finite cost
+constexpr int64_t kFrontsCapCells = 1 << 20;
+
+// biComputeTmap's two fronts (FastMarching.py:114-162) as one B = 2 batch -- map 0 from the goal
+// (g[0], g[1]), map 1 from the start (g[2], g[3]) -- over the device cost dcost (both maps), into
+// dT, then nodeJoin (*best) and the partial fields.  The fronts only matter up to their meeting,
+// so by default (EIK_OPT_FRONTS_CAP) each is solved only up to a cap on T estimated from a coarse
+// copy of the raster (bidir.hip "capped fronts"); a capped result that cannot be shown equal to
+// the full one (meeting rank at or above a front's kept cells, a band cell cut off, no meeting)
+// is replaced by the uncapped solve.
+int solve_fronts(eik_ctx* c, eik_fim2d* f, double* dcost, double* dT, const int64_t g[4], int64_t H, int64_t W,
+                 unsigned long long* best) {
+    hipStream_t st = c->stream;
+    const int64_t n = H * W;
+    const int64_t src[2] = {g[1] * W + g[0], g[3] * W + g[2]};
+    for (int64_t& v : c->fronts_info) v = 0;  // (join_and_partial fills the band entries)
+    for (auto& v : c->exact_info) v = 0;
+    // exact band: the fronts in the reference's arithmetic, so the replay mostly confirms their values
+    struct RefArith {
+        eik_fim2d* f;
+        RefArith(eik_fim2d* f_, bool on) : f(f_) { f->a.ref_arith = on ? 1 : 0; }
+        ~RefArith() { f->a.ref_arith = 0; }
+    } ref_guard(f, c->exact_band);
+    HIPCHK(c, c->work.ensure(bidir_join_work_bytes(n)));
+    const bool capped = c->fronts_cap > 0 && n >= kFrontsCapCells && std::min(H, W) >= 256;
+    if (capped) {
+        // coarse side 512 (EIK_FRONTS_COARSE, diagnostics): 256 / 1024 were slower at 4096^2
+        // (profiles/r04t_fronts_coarse_side.log: looser caps / a longer coarse chain)
+        static const int64_t cside = getenv("EIK_FRONTS_COARSE") ? std::max(64, atoi(getenv("EIK_FRONTS_COARSE"))) : 512;
+        const int64_t F = std::max<int64_t>(4, (std::max(H, W) + cside - 1) / cside);
+        const int64_t Hc = (H + F - 1) / F, Wc = (W + F - 1) / F, nc = Hc * Wc;
+        const size_t cb = sizeof(double) * 2 * nc;
+        HIPCHK(c, c->fronts.ensure(2 * cb + 256));
+        double* ccost = (double*)c->fronts.p;
+        double* cT = ccost + 2 * nc;
+        FrontsCheck* chk = (FrontsCheck*)((char*)c->fronts.p + 2 * cb);
+        HIPCHK(c, fronts_coarse_cost(dcost, H, W, (int)F, ccost, Hc, Wc, chk, st));
+        HIPCHK(c, hipMemcpyAsync(ccost + nc, ccost, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
+        eik_fim2d* fc = nullptr;
+        int rc = cached_solver(c, c->cached_fronts, 2, Hc, Wc, EIK_F64, kTile, &fc);
+        if (rc) return rc;
+        const int64_t gc[4] = {g[0] / F, g[1] / F, g[2] / F, g[3] / F};
+        const eik_stats keep = c->last;  // the coarse estimate's solve is not the caller's
+        int64_t keep_form[4];
+        memcpy(keep_form, c->last_form, sizeof keep_form);
+        rc = eik_fim2d_solve(fc, ccost, cT, gc, st);
+        c->last = keep;
+        memcpy(c->last_form, keep_form, sizeof keep_form);
+        if (rc) return rc;
+        HIPCHK(c, fronts_estimate(cT, cT + nc, nc, c->work.p, (double)F, c->fronts_cap, chk, st));
+        f->a.tcap = chk->caps;
+        rc = eik_fim2d_solve(f, dcost, dT, g, st);
+        f->a.tcap = nullptr;
+        if (rc) return rc;
+        HIPCHK(c, fronts_clean(dT, n, chk, st));
+        FrontsCheck h{};
+        int64_t mem[2] = {0, 0};
+        rc = join_and_partial(c, dT, n, H, W, best, mem, dcost, chk, &h, src);
+        if (rc) return rc;
+        const unsigned long long k = *best >> 30;
+        const bool ok = *best != ~0ull && h.viol == 0 && k < h.kept[0] && k < h.kept[1];
+        c->fronts_info[0] = std::isfinite(h.caps[0]) || std::isfinite(h.caps[1]);
+        c->fronts_info[2] = h.kept[0];
+        c->fronts_info[3] = h.kept[1];
+        c->fronts_info[4] = mem[0];
+        c->fronts_info[5] = mem[1];
+        if (ok || !c->fronts_info[0]) return EIK_OK;  // (no finite cap: that was the full solve)
+        c->fronts_info[1] = 1;  // the capped fronts did not settle the join: solve them in full
+    }
+    int rc = eik_fim2d_solve(f, dcost, dT, g, st);
+    if (rc) return rc;
+    int64_t mem[2] = {0, 0};
+    rc = join_and_partial(c, dT, n, H, W, best, mem, dcost, nullptr, nullptr, src);
+    if (!capped) {
+        c->fronts_info[4] = mem[0];
+        c->fronts_info[5] = mem[1];
+    }
+    return rc;
+}
+
+}  // namespace eik_api
+
 extern "C" {
 
 int eik_tmap2d_update_seeds_f32(eik_ctx* c, const float* cost_new, float* T, int64_t H, int64_t W, const int64_t* seeds_old,
@@ -2277,163 +2212,6 @@ int eik_tmap2d_f64(eik_ctx* c, const double* cost, int64_t H, int64_t W, int64_t
 int eik_tmap2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,
                          float* T) {
     return tmap_host<float>(c, cost, B, H, W, goals, T);
-}
-
-// nodeJoin + partial fields from the two device-resident full fields dT[0:n] (goal front) and
-// dT[n:2n] (start front), in place; *best = the packed join (~0: the fronts never meet).  d_cost
-// (the fronts' raster): band cells by the band relaxation (bidir.hip), else at their full-field
-// values; d_chk: the capped fronts' check.  Ends with the stream synchronised on *best.
-// src (with d_cost): the goal's and the start's linear index, for EIK_OPT_EXACT_BAND's replay.
-static int join_and_partial(eik_ctx* c, double* dT, int64_t n, int64_t H, int64_t W, unsigned long long* best,
-                            int64_t members[2], const double* d_cost = nullptr, FrontsCheck* d_chk = nullptr,
-                            FrontsCheck* h_chk = nullptr, const int64_t* src = nullptr) {
-    hipStream_t st = c->stream;
-    HIPCHK(c, c->work.ensure(bidir_join_work_bytes(n)));
-    HIPCHK(c, c->misc.ensure(64));
-    HIPCHK(c, bidir_join(dT, dT + n, n, c->work.p, c->work.bytes, (unsigned long long*)c->misc.p, st, members));
-    if (d_cost && src && c->exact_band && members[0] > 0 && members[1] > 0) {
-        // the reference's own band values, LIFO ties and nodeJoin, replayed from the join's ranks
-        const unsigned *rg = nullptr, *rs = nullptr;
-        bidir_join_ranks(c->work.p, n, &rg, &rs);
-        HIPCHK(c, c->exact.ensure(bidir_exact_work_bytes(n, members[0], members[1])));
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        HIPCHK(c, hipEventCreate(&e0));
-        HIPCHK(c, hipEventCreate(&e1));
-        HIPCHK(c, hipEventRecord(e0, st));
-        unsigned long long info[4] = {0, 0, 0, 0};
-        const hipError_t e = bidir_exact(dT, dT + n, d_cost, H, W, src[0], src[1], rg, rs, members, c->exact.p,
-                                         c->exact.bytes, (unsigned long long*)c->misc.p, st, info);
-        if (e == hipErrorNotReady || e == hipErrorNotSupported || e == hipErrorIllegalState) {
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
-            return set_err(c, EIK_ERR_NOCONVERGE,
-                           e == hipErrorNotReady      ? "biComputeTmap: the exact band replay did not settle"
-                           : e == hipErrorNotSupported ? "biComputeTmap: the exact band replay met a run of more than "
-                                                         "4096 cells of exactly equal T (a zero-cost region)"
-                                                       : "biComputeTmap: the exact meeting is not clear of the ranked "
-                                                         "cells' bound");
-        }
-        HIPCHK(c, e);
-        HIPCHK(c, hipEventRecord(e1, st));
-        HIPCHK(c, hipMemcpyAsync(best, c->misc.p, sizeof *best, hipMemcpyDeviceToHost, st));
-        HIPCHK(c, hipStreamSynchronize(st));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        for (int q = 0; q < 4; ++q) c->exact_info[q] = info[q];
-        c->exact_info[4] = (unsigned long long)(ms * 1000.0f);
-        for (int q = 0; q < 4; ++q) c->fronts_info[6 + q] = 0;
-        if (d_chk) {
-            HIPCHK(c, hipMemcpyAsync(h_chk, d_chk, sizeof *h_chk, hipMemcpyDeviceToHost, st));
-            HIPCHK(c, hipStreamSynchronize(st));
-            h_chk->viol = 0;  // band values come from the replay's events, not from the capped field
-        }
-        return EIK_OK;
-    }
-    {
-        const hipError_t e = bidir_partial(dT, dT + n, H, W, c->work.p, (const unsigned long long*)c->misc.p, st, d_cost,
-                                           d_chk ? &d_chk->viol : nullptr);
-        if (e == hipErrorNotReady)
-            return set_err(c, EIK_ERR_NOCONVERGE, "biComputeTmap: the band relaxation of the partial fields did not settle");
-        HIPCHK(c, e);
-    }
-    if (d_cost) {
-        unsigned bs[4] = {0, 0, 0, 0};
-        HIPCHK(c, bidir_band_stats(c->work.p, n, bs, st));
-        for (int q = 0; q < 4; ++q) c->fronts_info[6 + q] = bs[q];
-    }
-    HIPCHK(c, hipMemcpyAsync(best, c->misc.p, sizeof *best, hipMemcpyDeviceToHost, st));
-    if (d_chk) HIPCHK(c, hipMemcpyAsync(h_chk, d_chk, sizeof *h_chk, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return EIK_OK;
-}
-
-// Capped fronts: rasters of at least kFrontsCapCells cells, F x F coarse blocks with F =
-// max(4, ceil(max(H, W) / 512)), cap = F x (coarse T at the join bound's rank K0, bidir.hip
-// fronts_estimate) x margin (kFrontsMargin, EIK_OPT_FRONTS_CAP) + the largest finite cost
-constexpr int64_t kFrontsCapCells = 1 << 20;
-
-// biComputeTmap's two fronts (FastMarching.py:114-162) as one B = 2 batch -- map 0 from the goal
-// (g[0], g[1]), map 1 from the start (g[2], g[3]) -- over the device cost dcost (both maps), into
-// dT, then nodeJoin (*best) and the partial fields.  The fronts only matter up to their meeting,
-// so by default (EIK_OPT_FRONTS_CAP) each is solved only up to a cap on T estimated from a coarse
-// copy of the raster (bidir.hip "capped fronts"); a capped result that cannot be shown equal to
-// the full one (meeting rank at or above a front's kept cells, a band cell cut off, no meeting)
-// is replaced by the uncapped solve.
-static int solve_fronts(eik_ctx* c, eik_fim2d* f, double* dcost, double* dT, const int64_t g[4], int64_t H, int64_t W,
-                        unsigned long long* best) {
-    hipStream_t st = c->stream;
-    const int64_t n = H * W;
-    const int64_t src[2] = {g[1] * W + g[0], g[3] * W + g[2]};
-    for (int64_t& v : c->fronts_info) v = 0;  // (join_and_partial fills the band entries)
-    for (auto& v : c->exact_info) v = 0;
-    // exact band: the fronts in the reference's arithmetic, so the replay mostly confirms their values
-    struct RefArith {
-        eik_fim2d* f;
-        RefArith(eik_fim2d* f_, bool on) : f(f_) { f->a.ref_arith = on ? 1 : 0; }
-        ~RefArith() { f->a.ref_arith = 0; }
-    } ref_guard(f, c->exact_band);
-    HIPCHK(c, c->work.ensure(bidir_join_work_bytes(n)));
-    const bool capped = c->fronts_cap > 0 && n >= kFrontsCapCells && std::min(H, W) >= 256;
-    if (capped) {
-        // coarse side 512 (EIK_FRONTS_COARSE, diagnostics): 256 / 1024 were slower at 4096^2
-        // (profiles/r04t_fronts_coarse_side.log: looser caps / a longer coarse chain)
-        static const int64_t cside = getenv("EIK_FRONTS_COARSE") ? std::max(64, atoi(getenv("EIK_FRONTS_COARSE"))) : 512;
-        const int64_t F = std::max<int64_t>(4, (std::max(H, W) + cside - 1) / cside);
-        const int64_t Hc = (H + F - 1) / F, Wc = (W + F - 1) / F, nc = Hc * Wc;
-        const size_t cb = sizeof(double) * 2 * nc;
-        HIPCHK(c, c->fronts.ensure(2 * cb + 256));
-        double* ccost = (double*)c->fronts.p;
-        double* cT = ccost + 2 * nc;
-        FrontsCheck* chk = (FrontsCheck*)((char*)c->fronts.p + 2 * cb);
-        HIPCHK(c, fronts_coarse_cost(dcost, H, W, (int)F, ccost, Hc, Wc, chk, st));
-        HIPCHK(c, hipMemcpyAsync(ccost + nc, ccost, sizeof(double) * nc, hipMemcpyDeviceToDevice, st));
-        eik_fim2d* fc = c->cached_fronts;
-        if (!fc || fc->H != Hc || fc->W != Wc) {
-            if (fc) eik_fim2d_destroy(fc);
-            c->cached_fronts = nullptr;
-            int rc = eik_fim2d_create(c, 2, Hc, Wc, EIK_F64, &fc);
-            if (rc) return rc;
-            c->cached_fronts = fc;
-        }
-        const int64_t gc[4] = {g[0] / F, g[1] / F, g[2] / F, g[3] / F};
-        const eik_stats keep = c->last;  // the coarse estimate's solve is not the caller's
-        int64_t keep_form[4];
-        memcpy(keep_form, c->last_form, sizeof keep_form);
-        int rc = eik_fim2d_solve(fc, ccost, cT, gc, st);
-        c->last = keep;
-        memcpy(c->last_form, keep_form, sizeof keep_form);
-        if (rc) return rc;
-        HIPCHK(c, fronts_estimate(cT, cT + nc, nc, c->work.p, (double)F, c->fronts_cap, chk, st));
-        f->a.tcap = chk->caps;
-        rc = eik_fim2d_solve(f, dcost, dT, g, st);
-        f->a.tcap = nullptr;
-        if (rc) return rc;
-        HIPCHK(c, fronts_clean(dT, n, chk, st));
-        FrontsCheck h{};
-        int64_t mem[2] = {0, 0};
-        rc = join_and_partial(c, dT, n, H, W, best, mem, dcost, chk, &h, src);
-        if (rc) return rc;
-        const unsigned long long k = *best >> 30;
-        const bool ok = *best != ~0ull && h.viol == 0 && k < h.kept[0] && k < h.kept[1];
-        c->fronts_info[0] = std::isfinite(h.caps[0]) || std::isfinite(h.caps[1]);
-        c->fronts_info[2] = h.kept[0];
-        c->fronts_info[3] = h.kept[1];
-        c->fronts_info[4] = mem[0];
-        c->fronts_info[5] = mem[1];
-        if (ok || !c->fronts_info[0]) return EIK_OK;  // (no finite cap: that was the full solve)
-        c->fronts_info[1] = 1;  // the capped fronts did not settle the join: solve them in full
-    }
-    int rc = eik_fim2d_solve(f, dcost, dT, g, st);
-    if (rc) return rc;
-    int64_t mem[2] = {0, 0};
-    rc = join_and_partial(c, dT, n, H, W, best, mem, dcost, nullptr, nullptr, src);
-    if (!capped) {
-        c->fronts_info[4] = mem[0];
-        c->fronts_info[5] = mem[1];
-    }
-    return rc;
 }
 
 int eik_exact_info(const eik_ctx* c, int64_t out[5]) {
@@ -2522,370 +2300,6 @@ int eik_bidir_join_f64(eik_ctx* c, const double* TG, const double* TS, int64_t H
     return EIK_OK;
 }
 
-int eik_selftest_walker_math(eik_ctx* c, int64_t n, uint64_t seed, int64_t mismatches[6]) {
-    if (!c || !mismatches || n < 1) return EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->misc.ensure(64));
-    unsigned long long* d = (unsigned long long*)c->misc.p;
-    HIPCHK(c, hipMemsetAsync(d, 0, 6 * sizeof(unsigned long long), c->stream));
-    HIPCHK(c, walker_math_selftest((long long)n, (unsigned long long)seed, d, c->stream));
-    unsigned long long h[6];
-    HIPCHK(c, hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int k = 0; k < 6; ++k) mismatches[k] = (int64_t)h[k];
-    return EIK_OK;
-}
-
-static long path_steps(double tau) { return (long)std::nearbyint(15000.0 / tau); }  // round(15000/tau), FastMarching.py:173
-
-// the walk's arguments of the two single-path 2D device entries, from theirs
-static Gdm2dArgs path2d_args(const void* d_T, int64_t H, int64_t W, const double init[2], const double end[2], double tau,
-                             double* d_out, int64_t cap, int64_t* d_n_out, int* d_status, int fused) {
-    Gdm2dArgs a;
-    a.T = d_T;
-    a.H = H;
-    a.W = W;
-    a.ix = init[0];
-    a.iy = init[1];
-    a.ex = end[0];
-    a.ey = end[1];
-    a.tau = tau;
-    a.steps = path_steps(tau);
-    a.out = d_out;
-    a.cap = cap;
-    a.n_out = d_n_out;
-    a.status = d_status;
-    a.fused = fused;
-    return a;
-}
-
-int eik_path2d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, const double init[2],
-                   const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
-                   void* stream) {
-    if (!c || !d_T || !init || !end || !d_out || !d_n_out || !d_status || cap < 2 || H < 3 || W < 3 || !(tau > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad path arguments") : EIK_ERR_ARG;
-    const Gdm2dArgs a = path2d_args(d_T, H, W, init, end, tau, d_out, cap, d_n_out, d_status, c->path_loop);
-    HIPCHK(c, gdm2d(a, dtype == EIK_F64, (hipStream_t)stream));
-    return EIK_OK;
-}
-
-extern "C++" {  // (a template among the C entries)
-// The synchronous single-path host entries (dim = 2 or 3) after their own argument checks: the field
-// (`cells` values) to c->T2; the device results in c->work, out [cap][dim] | n | info [4] (has_info)
-// | status; launch(d_out, d_n, d_st, d_info), an entry's *_dev call on c->stream; then n, status
-// and the info words, and the n rows.
-template <typename Launch>
-static int path_host(eik_ctx* c, int dim, const double* T, int64_t cells, double* out, int64_t cap, int64_t* n_out,
-                     int* status, bool has_info, int64_t* info, Launch&& launch) {
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->T2.ensure(sizeof(double) * cells));
-    HIPCHK(c, c->work.ensure(sizeof(double) * dim * cap + (has_info ? 128 : 64)));
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * cells, c->stream));
-    double* d_out = (double*)c->work.p;
-    int64_t* d_n = (int64_t*)(d_out + dim * cap);
-    int64_t* d_info = has_info ? d_n + 1 : nullptr;
-    int* d_st = (int*)(d_n + (has_info ? 5 : 1));
-    int rc = launch(d_out, d_n, d_st, d_info);
-    if (rc) return rc;
-    int64_t h[5] = {0, 0, 0, 0, 0};  // n | info
-    int st = 0;
-    HIPCHK(c, hipMemcpyAsync(h, d_n, sizeof(int64_t) * (has_info ? 5 : 1), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    const int64_t nn = h[0] > cap ? cap : h[0];
-    // (as the entries always did: the safe one skips the copy of no rows, the others issue it)
-    if (nn > 0 || !has_info) HIPCHK(c, hipMemcpy(out, d_out, sizeof(double) * dim * nn, hipMemcpyDeviceToHost));
-    *n_out = nn;
-    *status = st;
-    if (info)
-        for (int k = 0; k < 4; ++k) info[k] = h[1 + k];
-    return EIK_OK;
-}
-}  // extern "C++"
-
-int eik_path2d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, const double init[2], const double end[2],
-                   double tau, double* out, int64_t cap, int64_t* n_out, int* status) {
-    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    return path_host(c, 2, T, H * W, out, cap, n_out, status, false, nullptr,
-                     [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
-                         return eik_path2d_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, c->stream);
-                     });
-}
-
-// ---- batched paths: P walks in one launch (gdm.hip: gdm2d_kernel / gdm3d_kernel on GdmBatchArgs)
-constexpr size_t kDescBlocks = 8;  // descriptor blocks kept per context
-
-// A descriptor block of >= P entries that no earlier call still uses: a block whose event has
-// completed (grown if too small), else a new one, else -- kDescBlocks calls in flight -- the oldest,
-// after waiting for it.
-static int stage_desc(eik_ctx* c, int64_t P, DescBlock** out) {
-    DescBlock* b = nullptr;
-    for (DescBlock& k : c->desc)
-        if (hipEventQuery(k.ev) == hipSuccess && (!b || (b->cap < P && k.cap >= P))) b = &k;
-    if (!b && c->desc.size() < kDescBlocks) {
-        c->desc.emplace_back();
-        b = &c->desc.back();
-        HIPCHK(c, hipEventCreateWithFlags(&b->ev, hipEventDisableTiming));
-    }
-    if (!b) {
-        b = &c->desc[c->desc_next++ % c->desc.size()];
-        HIPCHK(c, hipEventSynchronize(b->ev));
-    }
-    if (b->cap < P) {
-        if (b->h) (void)hipHostFree(b->h);
-        if (b->d) (void)hipFree(b->d);
-        b->h = b->d = nullptr;
-        b->cap = 0;
-        const int64_t cap = std::max<int64_t>(256, P);
-        HIPCHK(c, hipHostMalloc((void**)&b->h, sizeof(GdmDesc) * cap));
-        HIPCHK(c, hipMalloc((void**)&b->d, sizeof(GdmDesc) * cap));
-        b->cap = cap;
-    }
-    *out = b;
-    return EIK_OK;
-}
-
-// Host-side checks (batch_check) and staging (batch_stage) shared by the 2D and 3D batch entries
-// (dim = 2 or 3): on EIK_OK a.desc holds the P descriptors, on the device in stream order, and *blk
-// is to be marked busy (hipEventRecord on st) after the launch.  Nothing is launched on an error.
-static int batch_check(eik_ctx* c, int dim, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
-                       const int32_t* map_of, const double* inits, const double* ends, double tau, int64_t cap) {
-    if (!inits || !ends) return set_err(c, EIK_ERR_ARG, "batched path: NULL argument");
-    if (B < 1) return set_err(c, EIK_ERR_ARG, "batched path: B = %ld fields (>= 1 needed)", (long)B);
-    if (P < 1 || P > 0x7fffffff) return set_err(c, EIK_ERR_ARG, "batched path: P = %ld paths (1 .. 2^31 - 1)", (long)P);
-    if (cap < 2) return set_err(c, EIK_ERR_ARG, "batched path: cap = %ld rows per path (>= 2 needed)", (long)cap);
-    if (!(tau > 0)) return set_err(c, EIK_ERR_ARG, "batched path: tau = %g (> 0 needed)", tau);
-    if (dim == 2 ? (H < 3 || W < 3) : (H < 1 || W < 1 || L < 1))
-        return set_err(c, EIK_ERR_ARG, "batched path: field of %ld x %ld x %ld too small", (long)H, (long)W, (long)L);
-    if (!map_of && P != B && B != 1)
-        return set_err(c, EIK_ERR_ARG, "batched path: map_of is NULL with P = %ld paths on B = %ld fields (P == B or B == 1)",
-                       (long)P, (long)B);
-    if (map_of)
-        for (int64_t p = 0; p < P; ++p)
-            if (map_of[p] < 0 || map_of[p] >= B)
-                return set_err(c, EIK_ERR_ARG, "batched path: map_of[%ld] = %d outside [0, %ld)", (long)p, map_of[p], (long)B);
-    return EIK_OK;
-}
-static int batch_stage(eik_ctx* c, int dim, const void* d_T, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
-                       const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
-                       int64_t cap, int64_t* d_n_out, int* d_status, hipStream_t st, GdmBatchArgs& a, DescBlock** blk) {
-    if (!c) return EIK_ERR_ARG;
-    if (!d_T || !d_out || !d_n_out || !d_status) return set_err(c, EIK_ERR_ARG, "batched path: NULL argument");
-    int rc = batch_check(c, dim, B, H, W, L, P, map_of, inits, ends, tau, cap);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    rc = stage_desc(c, P, blk);
-    if (rc) return rc;
-    GdmDesc* h = (*blk)->h;
-    for (int64_t p = 0; p < P; ++p) {
-        h[p].map = map_of ? map_of[p] : B == 1 ? 0 : (int32_t)p;
-        h[p].pad = 0;
-        for (int k = 0; k < 3; ++k) {
-            h[p].init[k] = k < dim ? inits[dim * p + k] : 0.0;
-            h[p].end[k] = k < dim ? ends[dim * p + k] : 0.0;
-        }
-    }
-    HIPCHK(c, hipMemcpyAsync((*blk)->d, h, sizeof(GdmDesc) * P, hipMemcpyHostToDevice, st));
-    a.T = d_T;
-    a.H = H;
-    a.W = W;
-    a.L = L;
-    a.P = P;
-    a.desc = (*blk)->d;
-    a.tau = tau;
-    a.steps = path_steps(tau);
-    a.out = d_out;
-    a.cap = cap;
-    a.n_out = d_n_out;
-    a.status = d_status;
-    a.fused = c->path_loop;
-    return EIK_OK;
-}
-
-// The synchronous host entries' tail: path p's n_out[p] rows into out + p * cap * dim (rows past
-// them stay as the caller left them), after the walks on c->stream.
-static int batch_fetch(eik_ctx* c, int dim, int64_t P, int64_t cap, const double* d_out, const int64_t* d_n,
-                       const int* d_st, double* out, int64_t* n_out, int* status) {
-    HIPCHK(c, hipMemcpyAsync(n_out, d_n, sizeof(int64_t) * P, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(status, d_st, sizeof(int) * P, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int64_t p = 0; p < P; ++p) {
-        if (n_out[p] > cap) n_out[p] = cap;
-        if (n_out[p] > 0)
-            HIPCHK(c, hipMemcpyAsync(out + p * cap * dim, d_out + p * cap * dim, sizeof(double) * dim * n_out[p],
-                                     hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-// the host entries' device results in c->work: out [P][cap][dim] | info [P][4] (d_info given) | n_out [P]
-// | status [P]
-static int batch_work(eik_ctx* c, int dim, int64_t P, int64_t cap, double** d_out, int64_t** d_n, int** d_st,
-                      int64_t** d_info = nullptr) {
-    HIPCHK(c, c->work.ensure(sizeof(double) * dim * cap * P + ((d_info ? 5 : 1) * sizeof(int64_t) + sizeof(int)) * P + 64));
-    *d_out = (double*)c->work.p;
-    int64_t* const words = (int64_t*)(*d_out + dim * cap * P);
-    if (d_info) *d_info = words;
-    *d_n = words + (d_info ? 4 * P : 0);
-    *d_st = (int*)(*d_n + P);
-    return EIK_OK;
-}
-
-extern "C++" {
-// The synchronous batched host entries (dim = 2 or 3) after their own argument checks: the B fields
-// (`cells` values in all) to c->T2, once; launch(d_out, d_n, d_st, d_info), an entry's *_batch_dev
-// call on c->stream; then the info words and batch_fetch.
-template <typename Launch>
-static int path_batch_host(eik_ctx* c, int dim, const double* T, int64_t cells, int64_t P, double* out, int64_t cap,
-                           int64_t* n_out, int* status, bool has_info, int64_t* info, Launch&& launch) {
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, c->T2.ensure(sizeof(double) * cells));
-    double* d_out;
-    int64_t *d_n, *d_info = nullptr;
-    int* d_st;
-    int rc = batch_work(c, dim, P, cap, &d_out, &d_n, &d_st, has_info ? &d_info : nullptr);
-    if (rc) return rc;
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * cells, c->stream));
-    rc = launch(d_out, d_n, d_st, d_info);
-    if (rc) {
-        (void)hipStreamSynchronize(c->stream);  // the upload still reads T
-        return rc;
-    }
-    if (info) HIPCHK(c, hipMemcpyAsync(info, d_info, sizeof(int64_t) * 4 * P, hipMemcpyDeviceToHost, c->stream));
-    return batch_fetch(c, dim, P, cap, d_out, d_n, d_st, out, n_out, status);
-}
-}  // extern "C++"
-
-int eik_path2d_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
-                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
-                         int64_t cap, int64_t* d_n_out, int* d_status, void* stream) {
-    GdmBatchArgs a{};
-    DescBlock* blk = nullptr;
-    int rc = batch_stage(c, 2, d_T, B, H, W, 1, P, map_of, inits, ends, tau, d_out, cap, d_n_out, d_status,
-                         (hipStream_t)stream, a, &blk);
-    if (rc) return rc;
-    HIPCHK(c, gdm2d_batch(a, dtype == EIK_F64, (hipStream_t)stream));
-    HIPCHK(c, hipEventRecord(blk->ev, (hipStream_t)stream));
-    return EIK_OK;
-}
-
-int eik_path2d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int64_t W, int64_t P, const int32_t* map_of,
-                         const double* inits, const double* ends, double tau, double* out, int64_t cap, int64_t* n_out,
-                         int* status) {
-    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched path: NULL argument") : EIK_ERR_ARG;
-    int rc = batch_check(c, 2, B, H, W, 1, P, map_of, inits, ends, tau, cap);
-    if (rc) return rc;
-    return path_batch_host(c, 2, T, B * H * W, P, out, cap, n_out, status, false, nullptr,
-                           [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
-                               return eik_path2d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau, d_out,
-                                                           cap, d_n, d_st, c->stream);
-                           });
-}
-
-// ---- the obstacle-safe 2D walker (gdm_safe.hip): the entries above with tau <= 1 and the info words
-static long safe_stall(double tau) { return std::max(16L, (long)std::ceil(8.0 / tau)); }  // S of the stall rule
-
-int eik_path2d_safe_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, const double init[2],
-                        const double end[2], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
-                        int64_t* d_info, void* stream) {
-    if (!c || !d_T || !init || !end || !d_out || !d_n_out || !d_status || cap < 2 || H < 3 || W < 3 || !(tau > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad path arguments") : EIK_ERR_ARG;
-    if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
-    GdmSafeArgs s;
-    s.a = path2d_args(d_T, H, W, init, end, tau, d_out, cap, d_n_out, d_status, 0);
-    s.stall = safe_stall(tau);
-    s.info = d_info;
-    HIPCHK(c, gdm2d_safe(s, dtype == EIK_F64, (hipStream_t)stream));
-    return EIK_OK;
-}
-
-int eik_path2d_safe_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, const double init[2], const double end[2],
-                        double tau, double* out, int64_t cap, int64_t* n_out, int* status, int64_t info[4]) {
-    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    if (!init || !end || cap < 2 || H < 3 || W < 3 || !(tau > 0)) return set_err(c, EIK_ERR_ARG, "bad path arguments");
-    if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
-    return path_host(c, 2, T, H * W, out, cap, n_out, status, true, info,
-                     [&](double* d_out, int64_t* d_n, int* d_st, int64_t* d_info) {
-                         return eik_path2d_safe_dev(c, c->T2.p, EIK_F64, H, W, init, end, tau, d_out, cap, d_n, d_st, d_info,
-                                                    c->stream);
-                     });
-}
-
-int eik_path2d_safe_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t P,
-                              const int32_t* map_of, const double* inits, const double* ends, double tau,
-                              double* d_out, int64_t cap, int64_t* d_n_out, int* d_status, int64_t* d_info,
-                              void* stream) {
-    if (c && tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
-    GdmSafeBatchArgs s{};
-    DescBlock* blk = nullptr;
-    int rc = batch_stage(c, 2, d_T, B, H, W, 1, P, map_of, inits, ends, tau, d_out, cap, d_n_out, d_status,
-                         (hipStream_t)stream, s.b, &blk);
-    if (rc) return rc;
-    s.stall = safe_stall(tau);
-    s.info = d_info;
-    HIPCHK(c, gdm2d_safe_batch(s, dtype == EIK_F64, (hipStream_t)stream));
-    HIPCHK(c, hipEventRecord(blk->ev, (hipStream_t)stream));
-    return EIK_OK;
-}
-
-int eik_path2d_safe_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int64_t W, int64_t P,
-                              const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
-                              int64_t cap, int64_t* n_out, int* status, int64_t* info) {
-    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched path: NULL argument") : EIK_ERR_ARG;
-    int rc = batch_check(c, 2, B, H, W, 1, P, map_of, inits, ends, tau, cap);
-    if (rc) return rc;
-    if (tau > 1) return set_err(c, EIK_ERR_ARG, "safe path: tau = %g (0 < tau <= 1 needed)", tau);
-    return path_batch_host(c, 2, T, B * H * W, P, out, cap, n_out, status, true, info,
-                           [&](double* d_out, int64_t* d_n, int* d_st, int64_t* d_info) {
-                               return eik_path2d_safe_batch_dev(c, c->T2.p, EIK_F64, B, H, W, P, map_of, inits, ends, tau,
-                                                                d_out, cap, d_n, d_st, d_info, c->stream);
-                           });
-}
-
-int eik_plan2d_batch_f32(eik_ctx* c, const float* cost, int64_t B, int64_t H, int64_t W, const int64_t* goals,
-                         const double* starts, double tau, double* paths, int64_t cap, int64_t* n_out, int* status,
-                         float* T_out) {
-    if (!c || !cost || !goals || !starts || !paths || !n_out || !status)
-        return c ? set_err(c, EIK_ERR_ARG, "batched plan: NULL argument") : EIK_ERR_ARG;
-    if (B < 1 || H < 3 || W < 3 || cap < 2 || !(tau > 0))
-        return set_err(c, EIK_ERR_ARG, "batched plan: B = %ld, field %ld x %ld, cap = %ld, tau = %g", (long)B, (long)H,
-                       (long)W, (long)cap, tau);
-    for (int64_t b = 0; b < B; ++b)
-        if (goals[2 * b] < 0 || goals[2 * b + 1] < 0 || goals[2 * b] >= W || goals[2 * b + 1] >= H)
-            return set_err(c, EIK_ERR_ARG, "goal (%ld, %ld) of map %ld outside %ldx%ld", (long)goals[2 * b],
-                           (long)goals[2 * b + 1], (long)b, (long)H, (long)W);
-    const int64_t n = B * H * W;
-    HIPCHK(c, hipSetDevice(c->device));
-    eik_fim2d* f = nullptr;
-    int rc = get_solver(c, B, H, W, EIK_F32, &f);
-    if (rc) return rc;
-    HIPCHK(c, c->cost.ensure(sizeof(float) * n));
-    HIPCHK(c, c->T.ensure(sizeof(float) * n));
-    double* d_out;
-    int64_t* d_n;
-    int* d_st;
-    rc = batch_work(c, 2, B, cap, &d_out, &d_n, &d_st);
-    if (rc) return rc;
-    HIPCHK(c, host_to_dev(c, c->cost.p, cost, sizeof(float) * n, c->stream));
-    rc = check_cost(c, cost, c->cost.p, n, c->stream);
-    if (rc) return rc;
-    rc = eik_fim2d_solve(f, c->cost.p, c->T.p, goals, c->stream);  // the B fields stay on the device
-    if (rc) return rc;
-    std::vector<double> ends(2 * B);
-    for (int64_t k = 0; k < 2 * B; ++k) ends[k] = (double)goals[k];
-    rc = eik_path2d_batch_dev(c, c->T.p, EIK_F32, B, H, W, B, nullptr, starts, ends.data(), tau, d_out, cap, d_n, d_st,
-                              c->stream);
-    if (rc) return rc;
-    rc = batch_fetch(c, 2, B, cap, d_out, d_n, d_st, paths, n_out, status);
-    if (rc) return rc;
-    if (T_out) {
-        HIPCHK(c, dev_to_host(c, T_out, c->T.p, sizeof(float) * n, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return EIK_OK;
-}
-
 // ------------------------------------------------------------------------------ 3D
 // How one persistent launch of a 3D driver ended, after its synchronisation: the queue error word's refusal
 // (who names the solver, budget_who prefixes the visit budget's text), else c->last's fields that both
@@ -2914,14 +2328,10 @@ static int solve_layered(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, i
                          int64_t K = 0) {
     const bool f64 = dtype == EIK_F64;
     const int th = fim2dl_rows(f64);
-    eik_fim2d*& slot = f64 ? c->cached_l64 : c->cached_l;
-    eik_fim2d* f = slot;
-    if (!f || f->H != H || f->W != W) {
-        if (f) eik_fim2d_destroy(f);
-        slot = nullptr;
-        int rc = fim2d_create_rows(c, 1, H, W, dtype, th, &f);
+    eik_fim2d* f = nullptr;
+    {
+        const int rc = cached_solver(c, f64 ? c->cached_l64 : c->cached_l, 1, H, W, dtype, th, &f);
         if (rc) return rc;
-        slot = f;
     }
     Fim2dArgs a = f->a;
     a.cost = d_cost;
@@ -2986,7 +2396,7 @@ static int solve_layered(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, i
         HIPCHK(c, hipMemcpyAsync(f->h_q, f->qctl.p, kQueueCtlBytes, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipMemcpyAsync(f->h_visits, (void*)f->a.visits, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
-        err = f->h_q[192 / 4];
+        err = f->h_q[kQErrorWord];
         if (!(err & 4u) || (err & 3u)) break;
     }
     c->last_solver3[0] = 1;  // eik_fim3d_last_solver
@@ -3111,7 +2521,7 @@ static int fim3d_solve_persist(eik_ctx* c, Fim3dArgs a, int64_t B, int dtype, co
     HIPCHK(c, hipMemcpyAsync(hq, c->q3ctl.p, kQueueCtlBytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(hv, c->q3vis.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
-    const int rc = persist3_outcome(c, hq[192 / 4], "3D solver", "3D solve: ", q.qbudget, e0, e1, hv[0]);
+    const int rc = persist3_outcome(c, hq[kQErrorWord], "3D solver", "3D solve: ", q.qbudget, e0, e1, hv[0]);
     if (rc) return rc;
     c->last.inplace_passes = (int64_t)hv[2];  // 3D: relaxation passes summed over the visits
     c->last.bytes_alg = (double)hv[0] * (f64 ? 8 : 4) * 3.0 * a.tx * a.ty * a.tz;
@@ -3209,32 +2619,9 @@ static int fim3d_solve_batch(eik_ctx* c, const void* d_cost, void* d_T, int64_t 
     return rc;
 }
 
-static int fim3d_solve_one(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
-                           const int64_t goal[3], hipStream_t st, int64_t stop_off);
-
 int eik_fim3d_solve(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
                     const int64_t goal[3], void* stream) {
     return fim3d_solve_one(c, d_cost, d_T, H, W, L, dtype, goal, (hipStream_t)stream, -1);
-}
-
-// one volume; stop_off >= 0: the caller applies the early exit at that cell afterwards
-static int fim3d_solve_one(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
-                           const int64_t goal[3], hipStream_t st, int64_t stop_off) {
-    if (!c || !d_cost || !d_T || !goal || H < 1 || W < 1 || L < 1)
-        return c ? set_err(c, EIK_ERR_ARG, "bad 3D arguments") : EIK_ERR_ARG;
-    if (goal[0] < 0 || goal[1] < 0 || goal[2] < 0 || goal[0] >= W || goal[1] >= H || goal[2] >= L)
-        return set_err(c, EIK_ERR_ARG, "goal (%ld,%ld,%ld) outside %ldx%ldx%ld", (long)goal[0], (long)goal[1],
-                       (long)goal[2], (long)H, (long)W, (long)L);
-    HIPCHK(c, hipSetDevice(c->device));
-    // (an fp64 early-exit solve stays on fim3d.hip: its solve3_ref keeps the reference's exact ties,
-    // which decide FM3D's closed set, DESIGN.md §3.7)
-    int z0 = 0, nl = 0;
-    if (!(stop_off >= 0 && dtype == EIK_F64)) {
-        const int rc = layered_route(c, d_cost, H, W, L, dtype, st, goal[2], goal[2], &z0, &nl);
-        if (rc) return rc;
-    }
-    if (nl > 0) return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, goal, dtype, st);
-    return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, goal, st, stop_off);
 }
 
 // ---- goal sets for 3D solves (fim3d.hip seeding, seeds.hip labels3d)
@@ -3345,10 +2732,32 @@ int eik_labels3d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t 
 
 }  // extern "C"
 
+namespace eik_api __attribute__((visibility("hidden"))) {
+
+// one volume; stop_off >= 0: the caller applies the early exit at that cell afterwards
+int fim3d_solve_one(eik_ctx* c, const void* d_cost, void* d_T, int64_t H, int64_t W, int64_t L, int dtype,
+                    const int64_t goal[3], hipStream_t st, int64_t stop_off) {
+    if (!c || !d_cost || !d_T || !goal || H < 1 || W < 1 || L < 1)
+        return c ? set_err(c, EIK_ERR_ARG, "bad 3D arguments") : EIK_ERR_ARG;
+    if (goal[0] < 0 || goal[1] < 0 || goal[2] < 0 || goal[0] >= W || goal[1] >= H || goal[2] >= L)
+        return set_err(c, EIK_ERR_ARG, "goal (%ld,%ld,%ld) outside %ldx%ldx%ld", (long)goal[0], (long)goal[1],
+                       (long)goal[2], (long)H, (long)W, (long)L);
+    HIPCHK(c, hipSetDevice(c->device));
+    // (an fp64 early-exit solve stays on fim3d.hip: its solve3_ref keeps the reference's exact ties,
+    // which decide FM3D's closed set, DESIGN.md §3.7)
+    int z0 = 0, nl = 0;
+    if (!(stop_off >= 0 && dtype == EIK_F64)) {
+        const int rc = layered_route(c, d_cost, H, W, L, dtype, st, goal[2], goal[2], &z0, &nl);
+        if (rc) return rc;
+    }
+    if (nl > 0) return solve_layered(c, d_cost, d_T, H, W, L, z0, nl, goal, dtype, st);
+    return fim3d_solve_batch(c, d_cost, d_T, 1, H, W, L, dtype, goal, st, stop_off);
+}
+
 // Linear index of `start` for the early exit of FastMarching3D.computeTmap (:141), or -1 when the
 // reference never pops it: start == goal (the goal is closed without a pop, :132-134) or outside
 // the volume.  A start on +inf cost is never popped either; the kernel sees T[start] = +inf then.
-static int64_t early_offset(const int64_t goal[3], const int64_t start[3], int64_t H, int64_t W, int64_t L) {
+int64_t early_offset(const int64_t goal[3], const int64_t start[3], int64_t H, int64_t W, int64_t L) {
     if (!start) return -1;
     if (start[0] < 0 || start[1] < 0 || start[2] < 0 || start[0] >= W || start[1] >= H || start[2] >= L) return -1;
     if (start[0] == goal[0] && start[1] == goal[1] && start[2] == goal[2]) return -1;
@@ -3397,6 +2806,8 @@ static int tmap3d_seeds_host(eik_ctx* c, const R* cost, int64_t H, int64_t W, in
     return rc ? rc : fetch_results(c, n, T, c->T.p, labels);
 }
 
+}  // namespace eik_api
+
 extern "C" {
 
 int eik_tmap3d_seeds_f32(eik_ctx* c, const float* cost, int64_t H, int64_t W, int64_t L, const int64_t* seeds,
@@ -3422,7 +2833,8 @@ int eik_fim3d_early_exit(eik_ctx* c, const void* d_cost, const void* d_T, void* 
         if (n >= (1ll << 29)) return set_err(c, EIK_ERR_ARG, "exact band replay: volumes of < 2^29 cells");
         HIPCHK(c, c->exact.ensure(fm3d_exact_work_bytes(n)));
         hipStream_t st = (hipStream_t)stream;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
+        EventPair ev;  // (destroyed on every return path)
+        hipEvent_t &e0 = ev.e0, &e1 = ev.e1;
         HIPCHK(c, hipEventCreate(&e0));
         HIPCHK(c, hipEventCreate(&e1));
         HIPCHK(c, hipEventRecord(e0, st));
@@ -3431,21 +2843,16 @@ int eik_fim3d_early_exit(eik_ctx* c, const void* d_cost, const void* d_T, void* 
         const hipError_t e = fm3d_exact(static_cast<const double*>(d_cost), static_cast<const double*>(d_T),
                                         static_cast<double*>(d_Te), H, W, L, goal_off, ts_off, c->exact.p,
                                         c->exact.bytes, st, info);
-        if (e == hipErrorNotReady || e == hipErrorNotSupported) {
-            (void)hipEventDestroy(e0);
-            (void)hipEventDestroy(e1);
+        if (e == hipErrorNotReady || e == hipErrorNotSupported)
             return set_err(c, EIK_ERR_NOCONVERGE, e == hipErrorNotReady
                                                       ? "FM3D early exit: the exact band replay did not settle"
                                                       : "FM3D early exit: the exact band replay met a run of more "
                                                         "than 4096 cells of exactly equal T (a zero-cost region)");
-        }
         HIPCHK(c, e);
         HIPCHK(c, hipEventRecord(e1, st));
         HIPCHK(c, hipEventSynchronize(e1));
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
         for (int q = 0; q < 4; ++q) c->exact_info[q] = info[q];
         c->exact_info[4] = (unsigned long long)(ms * 1000.0f);
         return EIK_OK;
@@ -3473,684 +2880,6 @@ int eik_tmap3d_early_f64(eik_ctx* c, const double* cost, int64_t H, int64_t W, i
                          const int64_t start[3], double* T) {
     if (!start) return c ? set_err(c, EIK_ERR_ARG, "NULL start") : EIK_ERR_ARG;
     return tmap3d_host<double>(c, cost, H, W, L, goal, start, T);
-}
-
-int eik_path3d_dev(eik_ctx* c, const void* d_T, int dtype, int64_t H, int64_t W, int64_t L, const double init[3],
-                   const double end[3], double tau, double* d_out, int64_t cap, int64_t* d_n_out, int* d_status,
-                   void* stream) {
-    if (!c || !d_T || !init || !end || !d_out || !d_n_out || !d_status || cap < 2 || !(tau > 0) || H < 1 || W < 1 ||
-        L < 1)
-        return c ? set_err(c, EIK_ERR_ARG, "bad 3D path arguments") : EIK_ERR_ARG;
-    Gdm3dArgs a;
-    a.T = d_T;
-    a.H = H;
-    a.W = W;
-    a.L = L;
-    for (int i = 0; i < 3; ++i) {
-        a.init[i] = init[i];
-        a.end[i] = end[i];
-    }
-    a.tau = tau;
-    a.steps = path_steps(tau);  // int(round(15000/tau)), FastMarching3D.py:207
-    a.out = d_out;
-    a.cap = cap;
-    a.n_out = d_n_out;
-    a.status = d_status;
-    HIPCHK(c, gdm3d(a, dtype == EIK_F64, (hipStream_t)stream));
-    return EIK_OK;
-}
-
-int eik_path3d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, int64_t L, const double init[3],
-                   const double end[3], double tau, double* out, int64_t cap, int64_t* n_out, int* status) {
-    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    return path_host(c, 3, T, H * W * L, out, cap, n_out, status, false, nullptr,
-                     [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
-                         return eik_path3d_dev(c, c->T2.p, EIK_F64, H, W, L, init, end, tau, d_out, cap, d_n, d_st, c->stream);
-                     });
-}
-
-int eik_path3d_batch_dev(eik_ctx* c, const void* d_T, int dtype, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
-                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* d_out,
-                         int64_t cap, int64_t* d_n_out, int* d_status, void* stream) {
-    GdmBatchArgs a{};
-    DescBlock* blk = nullptr;
-    int rc = batch_stage(c, 3, d_T, B, H, W, L, P, map_of, inits, ends, tau, d_out, cap, d_n_out, d_status,
-                         (hipStream_t)stream, a, &blk);
-    if (rc) return rc;
-    HIPCHK(c, gdm3d_batch(a, dtype == EIK_F64, (hipStream_t)stream));
-    HIPCHK(c, hipEventRecord(blk->ev, (hipStream_t)stream));
-    return EIK_OK;
-}
-
-int eik_path3d_batch_f64(eik_ctx* c, const double* T, int64_t B, int64_t H, int64_t W, int64_t L, int64_t P,
-                         const int32_t* map_of, const double* inits, const double* ends, double tau, double* out,
-                         int64_t cap, int64_t* n_out, int* status) {
-    if (!c || !T || !out || !n_out || !status) return c ? set_err(c, EIK_ERR_ARG, "batched 3D path: NULL argument") : EIK_ERR_ARG;
-    int rc = batch_check(c, 3, B, H, W, L, P, map_of, inits, ends, tau, cap);
-    if (rc) return rc;
-    return path_batch_host(c, 3, T, B * H * W * L, P, out, cap, n_out, status, false, nullptr,
-                           [&](double* d_out, int64_t* d_n, int* d_st, int64_t*) {
-                               return eik_path3d_batch_dev(c, c->T2.p, EIK_F64, B, H, W, L, P, map_of, inits, ends, tau,
-                                                           d_out, cap, d_n, d_st, c->stream);
-                           });
-}
-
-int eik_gradient2d_f64(eik_ctx* c, const double* T, int64_t H, int64_t W, double* gnx, double* gny) {
-    if (!c || !T || !gnx || !gny || H < 2 || W < 2) return c ? set_err(c, EIK_ERR_ARG, "bad arguments") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    HIPCHK(c, c->work.ensure(sizeof(double) * 2 * n));
-    HIPCHK(c, host_to_dev(c, c->T2.p, T, sizeof(double) * n, c->stream));
-    double* gx = (double*)c->work.p;
-    HIPCHK(c, gradient2d((const double*)c->T2.p, H, W, gx, gx + n, c->stream));
-    HIPCHK(c, dev_to_host(c, gnx, gx, sizeof(double) * n, c->stream));
-    HIPCHK(c, dev_to_host(c, gny, gx + n, sizeof(double) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------------------------------ cost-raster builder
-// image_filling (:82-94) of the device mask m in place: the pixels equal to m[0] that the
-// 4-connected flood fill from (0, 0) reaches.  Default: connected components (cm_fill_ccl,
-// union-find); EIK_FILL_FIM=1 in the build: reachability by the block-FIM solver on cost 0 / +inf.
-#ifndef EIK_FILL_FIM
-#define EIK_FILL_FIM 0
-#endif
-static int cm_fill(eik_ctx* c, unsigned char* m, int64_t H, int64_t W, float* fcost, float* fT, hipStream_t st) {
-#if EIK_FILL_FIM
-    eik_fim2d* f = c->cached_fill;
-    if (!f || f->H != H || f->W != W) {
-        if (f) eik_fim2d_destroy(f);
-        c->cached_fill = nullptr;
-        int rc = eik_fim2d_create(c, 1, H, W, EIK_F32, &f);
-        if (rc) return rc;
-        c->cached_fill = f;
-    }
-    HIPCHK(c, cm_fill_cost(m, H * W, fcost, st));
-    const int64_t goal[2] = {0, 0};
-    const eik_stats keep = c->last;  // the builder's internal solves do not count as the caller's
-    int64_t keep_form[4];
-    memcpy(keep_form, c->last_form, sizeof keep_form);
-    int rc = eik_fim2d_solve(f, fcost, fT, goal, st);
-    c->last = keep;
-    memcpy(c->last_form, keep_form, sizeof keep_form);
-    if (rc) return rc;
-    HIPCHK(c, cm_fill_apply(m, fT, H * W, st));
-#else
-    // the two f32 scratch planes serve as the int32 lroot / parent arrays
-    HIPCHK(c, cm_fill_ccl(m, H, W, reinterpret_cast<int*>(fcost), reinterpret_cast<int*>(fT), st));
-#endif
-    return EIK_OK;
-}
-
-// The builder's scratch: 3 masks, 3 int planes (column distances, squared EDT, envelope apexes),
-// 2 f32 (fill cost, fill T), 2 f64 planes, reduction words.  obst = the caller's device mask if given.
-struct cm_scratch {
-    unsigned char *obst, *tmp, *dil;
-    int *g, *D, *vbuf;
-    float *fcost, *fT;
-    double *work, *tmpd;
-    unsigned long long* red;
-};
-
-static int cm_scratch_get(eik_ctx* c, int64_t n, uint8_t* d_obst, cm_scratch* s) {
-    HIPCHK(c, c->cm_u8.ensure(3 * n + 64));
-    HIPCHK(c, c->cm_i32.ensure(sizeof(int) * 3 * n));
-    HIPCHK(c, c->cm_f32.ensure(sizeof(float) * 2 * n));
-    HIPCHK(c, c->cm_f64.ensure(sizeof(double) * 2 * n + 64));
-    s->obst = d_obst ? d_obst : (unsigned char*)c->cm_u8.p;
-    s->tmp = (unsigned char*)c->cm_u8.p + n;
-    s->dil = (unsigned char*)c->cm_u8.p + 2 * n;
-    s->g = (int*)c->cm_i32.p;
-    s->D = s->g + n;
-    s->vbuf = s->g + 2 * n;
-    s->fcost = (float*)c->cm_f32.p;
-    s->fT = s->fcost + n;
-    s->work = (double*)c->cm_f64.p;
-    s->tmpd = s->work + n;
-    s->red = (unsigned long long*)(s->tmpd + n);
-    return EIK_OK;
-}
-
-static const eik_costmap_params kCmDefaults = {0.20, 0.9, 1.0, 10.0, 300.0};
-
-// The cost tail (:1180-1216) on the device mask s.obst as it stands after :1177: obstacle border,
-// expansion dilation, distance ramp, cost, blur.  s.obst ends as the final obstacle map.
-static int cm_tail(eik_ctx* c, const cm_scratch& s, int64_t H, int64_t W, double res, const eik_costmap_params& p,
-                   double* d_cost, hipStream_t st) {
-    const int r3 = (int)std::nearbyint(p.expansion / res);                      // :1190-1191
-    HIPCHK(c, cm_border(s.obst, H, W, 1, st));                                  // :1180-1184
-    HIPCHK(c, cm_morph(s.obst, H, W, r3, false, s.dil, s.g, s.D, s.vbuf, st));  // :1192
-    HIPCHK(c, cm_edt_ramp(s.obst, H, W, r3, s.g, s.D, s.vbuf, st));  // :1194 (distance to obstacles, as :1196 uses it)
-    HIPCHK(c, cm_cost(s.obst, s.dil, s.D, H, W, res, p.high, p.gradient, s.work, s.tmpd, d_cost, s.red, st));  // :1187-1216
-    return EIK_OK;
-}
-
-extern "C" {
-
-int eik_costmap_dev(eik_ctx* c, const double* d_Z, int64_t H, int64_t W, double res, double size,
-                    const eik_costmap_params* params, double* d_cost, uint8_t* d_obst, void* stream) {
-    if (!c || !d_Z || !d_cost || H < 3 || W < 3 || !(res > 0) || !(size > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad cost-map arguments") : EIK_ERR_ARG;
-    const eik_costmap_params p = params ? *params : kCmDefaults;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)stream;
-    cm_scratch s;
-    int rc = cm_scratch_get(c, H * W, d_obst, &s);
-    if (rc) return rc;
-    const int r1 = 10;                                              // :1167
-    const int r2 = (int)std::nearbyint((p.diagonal / 2) / res);     // :1172-1173
-    HIPCHK(c, cm_normals(d_Z, H, W, size, s.red, p.slope_max, s.obst, nullptr, nullptr, nullptr, st));  // :1104-1160
-    // min(Z)'s key (red is reused below) for the rover path's z lookup (:1101, :1246): misc word 5
-    HIPCHK(c, c->misc.ensure(64));
-    HIPCHK(c, hipMemcpyAsync((unsigned long long*)c->misc.p + 5, s.red, sizeof(unsigned long long),
-                             hipMemcpyDeviceToDevice, st));
-    rc = cm_fill(c, s.obst, H, W, s.fcost, s.fT, st);                         // :1163-1164
-    if (rc) return rc;
-    HIPCHK(c, cm_morph(s.obst, H, W, r1, true, s.tmp, s.g, s.D, s.vbuf, st));  // :1168
-    HIPCHK(c, cm_morph(s.tmp, H, W, r1, false, s.obst, s.g, s.D, s.vbuf, st)); // :1169
-    HIPCHK(c, cm_morph(s.obst, H, W, r2, false, s.tmp, s.g, s.D, s.vbuf, st)); // :1175
-    rc = cm_fill(c, s.tmp, H, W, s.fcost, s.fT, st);                          // :1176
-    if (rc) return rc;
-    HIPCHK(c, cm_morph(s.tmp, H, W, r2, true, s.obst, s.g, s.D, s.vbuf, st));  // :1177
-    return cm_tail(c, s, H, W, res, p, d_cost, st);                           // :1180-1216
-}
-
-int eik_costmap_f64(eik_ctx* c, const double* Z, int64_t H, int64_t W, double res, double size,
-                    const eik_costmap_params* params, double* cost_out, uint8_t* obst_out) {
-    if (!c || !Z || !cost_out) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * 2 * n + n));
-    double* dZ = (double*)c->T2.p;
-    double* dC = dZ + n;
-    uint8_t* dO = (uint8_t*)(dC + n);
-    HIPCHK(c, host_to_dev(c, dZ, Z, sizeof(double) * n, c->stream));
-    int rc = eik_costmap_dev(c, dZ, H, W, res, size, params, dC, dO, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, cost_out, dC, sizeof(double) * n, c->stream));
-    if (obst_out) HIPCHK(c, dev_to_host(c, obst_out, dO, n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-int eik_cost_tail_u8(eik_ctx* c, const uint8_t* obst, int64_t H, int64_t W, double res,
-                     const eik_costmap_params* params, double* cost_out, uint8_t* obst_out) {
-    if (!c || !obst || !cost_out || H < 3 || W < 3 || !(res > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad cost-tail arguments") : EIK_ERR_ARG;
-    const eik_costmap_params p = params ? *params : kCmDefaults;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    cm_scratch s;
-    int rc = cm_scratch_get(c, n, nullptr, &s);
-    if (rc) return rc;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * n));
-    double* dC = (double*)c->T2.p;
-    HIPCHK(c, host_to_dev(c, s.obst, obst, n, c->stream));
-    rc = cm_tail(c, s, H, W, res, p, dC, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, cost_out, dC, sizeof(double) * n, c->stream));
-    if (obst_out) HIPCHK(c, dev_to_host(c, obst_out, s.obst, n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-int eik_surface_normal_f64(eik_ctx* c, const double* Z, int64_t H, int64_t W, double size, double* Nx, double* Ny,
-                           double* Nz) {
-    if (!c || !Z || !Nx || !Ny || !Nz || H < 3 || W < 3 || !(size > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad surface_normal arguments") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * 4 * n + 64));
-    double* dZ = (double*)c->T2.p;
-    unsigned long long* red = (unsigned long long*)(dZ + 4 * n);
-    HIPCHK(c, host_to_dev(c, dZ, Z, sizeof(double) * n, c->stream));
-    HIPCHK(c, cm_normals(dZ, H, W, size, red, 0.0, nullptr, dZ + n, dZ + 2 * n, dZ + 3 * n, c->stream));
-    HIPCHK(c, dev_to_host(c, Nx, dZ + n, sizeof(double) * n, c->stream));
-    HIPCHK(c, dev_to_host(c, Ny, dZ + 2 * n, sizeof(double) * n, c->stream));
-    HIPCHK(c, dev_to_host(c, Nz, dZ + 3 * n, sizeof(double) * n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-int eik_image_fill_u8(eik_ctx* c, const uint8_t* im, int64_t H, int64_t W, uint8_t* out) {
-    if (!c || !im || !out || H < 1 || W < 1) return c ? set_err(c, EIK_ERR_ARG, "bad image_filling arguments") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->cm_u8.ensure(3 * n + 64));
-    HIPCHK(c, c->cm_f32.ensure(sizeof(float) * 2 * n));
-    unsigned char* m = (unsigned char*)c->cm_u8.p;
-    HIPCHK(c, host_to_dev(c, m, im, n, c->stream));
-    float* fcost = (float*)c->cm_f32.p;
-    int rc = cm_fill(c, m, H, W, fcost, fcost + n, c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, out, m, n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-int eik_disk_morph_u8(eik_ctx* c, const uint8_t* im, int64_t H, int64_t W, int radius, int erode, uint8_t* out) {
-    if (!c || !im || !out || H < 1 || W < 1 || radius < 0)
-        return c ? set_err(c, EIK_ERR_ARG, "bad disk morphology arguments") : EIK_ERR_ARG;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = H * W;
-    HIPCHK(c, c->cm_u8.ensure(3 * n + 64));
-    HIPCHK(c, c->cm_i32.ensure(sizeof(int) * 3 * n));
-    unsigned char* a = (unsigned char*)c->cm_u8.p;
-    unsigned char* o = a + n;
-    int* g = (int*)c->cm_i32.p;
-    HIPCHK(c, host_to_dev(c, a, im, n, c->stream));
-    HIPCHK(c, cm_morph(a, H, W, radius, erode != 0, o, g, g + n, g + 2 * n, c->stream));
-    HIPCHK(c, dev_to_host(c, out, o, n, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-// ------------------------------------------------------- rover path (planner step 1, :1097-1258)
-int eik_rover_path_f64(eik_ctx* c, const double* Z, int64_t H, int64_t W, const eik_rover_query* q,
-                       const eik_costmap_params* params, double* path_xyz, double* heading, int64_t cap,
-                       int64_t* n_out, uint32_t join[2], double* cost_out) {
-    if (!c || !Z || !q || !path_xyz || !heading || !n_out || H < 3 || W < 3 || !(q->resolution > 0) ||
-        !(q->size > 0) || !(q->tau > 0))
-        return c ? set_err(c, EIK_ERR_ARG, "bad rover-path arguments") : EIK_ERR_ARG;
-    const int64_t n = H * W;
-    if (n >= (1ll << 29)) return set_err(c, EIK_ERR_ARG, "bidirectional join supports < 2^29 cells");
-    // nodes: int(round(v / res - 1)), Python's round = half to even   :1107-1117
-    const double res = q->resolution;
-    const int64_t g[4] = {(int64_t)std::nearbyint(q->xm / res - 1), (int64_t)std::nearbyint(q->ym / res - 1),
-                          (int64_t)std::nearbyint(q->xr / res - 1), (int64_t)std::nearbyint(q->yr / res - 1)};
-    for (int k = 0; k < 2; ++k)
-        if (g[2 * k] < 0 || g[2 * k + 1] < 0 || g[2 * k] >= W || g[2 * k + 1] >= H)
-            return set_err(c, EIK_ERR_ARG, "%s node (%ld, %ld) outside the %ldx%ld DEM", k ? "rover" : "sample",
-                           (long)g[2 * k], (long)g[2 * k + 1], (long)H, (long)W);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int64_t steps = (int64_t)std::nearbyint(15000.0 / q->tau);  // FastMarching.py:173
-    const int64_t pcap = steps + 4;
-    const size_t pbytes = sizeof(double) * 2 * 2 * pcap + 64;
-    HIPCHK(c, c->T2.ensure(std::max(sizeof(double) * n, pbytes)));  // Z, then (Z consumed) the paths
-    HIPCHK(c, c->cost.ensure(sizeof(double) * 2 * n));
-    HIPCHK(c, c->T.ensure(sizeof(double) * 2 * n));
-    double* dZ = (double*)c->T2.p;
-    double* dcost = (double*)c->cost.p;
-    double* dT = (double*)c->T.p;
-    // EIK_ROVER_PHASES=1 (diagnostics): synchronise after each phase and print its wall time
-    static const bool phases = getenv("EIK_ROVER_PHASES") != nullptr;
-    auto tp = std::chrono::steady_clock::now();
-    auto phase = [&](const char* name) {
-        if (!phases) return;
-        (void)hipStreamSynchronize(st);
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[rover] %-10s %8.3f ms\n", name, std::chrono::duration<double, std::milli>(now - tp).count());
-        tp = now;
-    };
-    phase("setup");
-    HIPCHK(c, host_to_dev(c, dZ, Z, sizeof(double) * n, st));
-    phase("dem_h2d");
-    int rc = eik_costmap_dev(c, dZ, H, W, res, q->size, params, dcost, nullptr, st);  // :1101-1216
-    if (rc) return rc;
-    phase("costmap");
-    // biComputeTmap(cMap.T, goal = sample node, start = rover node)   :1222; both fronts, one batch
-    HIPCHK(c, hipMemcpyAsync(dcost + n, dcost, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
-    if (cost_out) HIPCHK(c, dev_to_host(c, cost_out, dcost, sizeof(double) * n, st));
-    eik_fim2d* f = nullptr;
-    rc = get_solver(c, 2, H, W, EIK_F64, &f);
-    if (rc) return rc;
-    unsigned long long best = 0;
-    rc = solve_fronts(c, f, dcost, dT, g, H, W, &best);  // :114-162
-    if (rc) return rc;
-    phase("fronts");
-    if (best == ~0ull) return set_err(c, EIK_ERR_UNREACHABLE, "the rover cannot reach the sample");
-    const int64_t node = (int64_t)(best & ((1ull << 29) - 1));
-    const double jn[2] = {(double)(node % W), (double)(node / W)};
-    if (join) {
-        join[0] = (uint32_t)(node % W);
-        join[1] = (uint32_t)(node / W);
-    }
-    // pathG = getPathGDM(TmapG, nodeJoin, goal, tau), pathS = getPathGDM(TmapS, nodeJoin, start, tau)   :1225-1226
-    double* dP = (double*)c->T2.p;  // [pathG | pathS], then n_out[2], status[2]
-    int64_t* dn = (int64_t*)(dP + 2 * 2 * pcap);
-    int* dst = (int*)(dn + 2);
-    const double eg[2] = {(double)g[0], (double)g[1]}, es[2] = {(double)g[2], (double)g[3]};
-    // the two walks are independent one-workgroup kernels: pathS runs on a second stream beside
-    // pathG (each walk is one dependent chain of steps, ~0.4 us each)
-    if (!c->stream2) HIPCHK(c, hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    if (!c->ev_fork) HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-    if (!c->ev_join) HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_fork, st));
-    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    rc = eik_path2d_dev(c, dT, EIK_F64, H, W, jn, eg, q->tau, dP, pcap, dn, dst, st);
-    if (rc) return rc;
-    rc = eik_path2d_dev(c, dT + n, EIK_F64, H, W, jn, es, q->tau, dP + 2 * pcap, pcap, dn + 1, dst + 1, c->stream2);
-    if (rc) return rc;
-    HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-    HIPCHK(c, hipStreamWaitEvent(st, c->ev_join, 0));
-    phase("walks");
-    int64_t hn[2];
-    int hs[2];
-    unsigned long long zkey = 0;
-    HIPCHK(c, hipMemcpyAsync(hn, dn, sizeof hn, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(hs, dst, sizeof hs, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(&zkey, (unsigned long long*)c->misc.p + 5, sizeof zkey, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (hs[0] == EIK_PATH_ERROR || hs[1] == EIK_PATH_ERROR)
-        return set_err(c, EIK_ERR_ARG, "getPathGDM failed (the reference raises): NaN point or out of range");
-    std::vector<double> pg((size_t)(2 * hn[0])), ps((size_t)(2 * hn[1]));
-    HIPCHK(c, hipMemcpyAsync(pg.data(), dP, sizeof(double) * 2 * hn[0], hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(ps.data(), dP + 2 * pcap, sizeof(double) * 2 * hn[1], hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    phase("paths_d2h");
-    // the cost builder's min(Z), from its order-preserving key (costmap.hip dkey)
-    const unsigned long long zb = (zkey >> 63) ? (zkey & ~(1ull << 63)) : ~zkey;
-    double zmin;
-    memcpy(&zmin, &zb, sizeof zmin);
-    rc = rover_assemble(ps.data(), hn[1], pg.data(), hn[0], Z, H, W, q, path_xyz, heading, cap, n_out, zmin);
-    phase("assemble");
-    if (rc) return set_err(c, rc, *n_out > cap ? "path buffer too small (%ld rows needed)" : "waypoint outside the DEM",
-                           (long)*n_out);
-    return EIK_OK;
-}
-
-}  // extern "C"
-
-// ------------------------------------------- end-effector cost volume (planner step 3, :1462-1593)
-namespace {
-
-// The host side of arm.hip: the tables TunnelCost forms in Python floats (:515-519, :527-546,
-// :571-590, :621-631, :655-668, :683-703), in the reference's evaluation order.
-struct ArmTables {
-    std::vector<double> buf;  // toaA | toaB | toaC | I | K | norm | valA | ct | st | cs | ss | ks | valC
-    size_t oA = 0, oB = 0, oC = 0, oI = 0, oK = 0, oN = 0, oV = 0, oct = 0, ost = 0, ocs = 0, oss = 0, oks = 0, ovc = 0;
-    int nX = 0, nZ = 0, nK = 0;
-    double rad = 0;
-};
-
-void np_linspace(double a, double b, int64_t n, double* out) {
-#pragma clang fp contract(off)
-    if (n == 1) {
-        out[0] = a;
-        return;
-    }
-    const double div = (double)(n - 1), delta = b - a, step = delta / div;
-    for (int64_t i = 0; i < n; ++i) out[i] = step == 0 ? ((double)i / div) * delta + a : (double)i * step + a;
-    out[n - 1] = b;
-}
-
-void arm_toa(const double* h, const double* p, double yaw_off, double* t) {
-#pragma clang fp contract(off)
-    const double alpha = h[2] - yaw_off, beta = h[1], gamma = h[0];
-    const double ca = std::cos(alpha), cb = std::cos(beta), cg = std::cos(gamma);
-    const double sa = std::sin(alpha), sb = std::sin(beta), sg = std::sin(gamma);
-    const double r[12] = {ca * cb, ca * sb * sg - sa * cg, ca * sb * cg + sa * sg, p[0],
-                          sa * cb, sa * sb * sg + ca * cg, sa * sb * cg - ca * sg, p[1],
-                          -sb,     cb * sg,                cb * cg,                p[2]};
-    for (int i = 0; i < 12; ++i) t[i] = r[i];
-}
-
-void arm_tables(const double* gamma2D, const double* heading, int64_t npts, const eik_arm_volume& v, ArmTables& T) {
-#pragma clang fp contract(off)
-    const double gradient = 15.0;                                              // :512
-    const double tunnelRad = v.rlim + 2 * v.resX;                              // :515
-    T.nX = (int)(std::nearbyint(2 * tunnelRad / v.resX) + 1);                  // :516
-    T.nZ = (int)(std::nearbyint(2 * tunnelRad / v.resZ) + 1);                  // :517
-    T.nK = (int)std::nearbyint(T.nZ / 2.0) + 1;                                // :671
-    T.rad = v.rlim + 2 * v.resZ;                                               // :688-690
-    const size_t nik = (size_t)T.nX * T.nZ;
-    size_t o = 0;
-    T.oA = o; o += 12 * (size_t)npts;
-    T.oB = o; o += 12;
-    T.oC = o; o += 12;
-    T.oI = o; o += T.nX;
-    T.oK = o; o += T.nZ;
-    T.oN = o; o += nik;
-    T.oV = o; o += nik;
-    T.oct = o; o += 100;
-    T.ost = o; o += 100;
-    T.ocs = o; o += 90;
-    T.oss = o; o += 90;
-    T.oks = o; o += T.nK;
-    T.ovc = o; o += T.nK;
-    T.buf.assign(o, 0.0);
-    double* b = T.buf.data();
-    const double half_pi = 3.141592653589793 / 2;  // math.pi / 2
-    for (int64_t j = 0; j < npts; ++j) arm_toa(heading + 3 * j, gamma2D + 3 * j, half_pi, b + T.oA + 12 * j);
-    arm_toa(heading, gamma2D, half_pi, b + T.oB);                                          // :617-631
-    arm_toa(heading + 3 * (npts - 1), gamma2D + 3 * (npts - 1), 0.0, b + T.oC);            // :655-668
-    np_linspace(-tunnelRad, tunnelRad, T.nX, b + T.oI);                                     // :563
-    np_linspace(-tunnelRad, tunnelRad, T.nZ, b + T.oK);                                     // :564
-    const double c = (v.rO + v.rm) / 2;
-    for (int i = 0; i < T.nX; ++i)
-        for (int k = 0; k < T.nZ; ++k) {
-            const double I = b[T.oI + i], K = b[T.oK + k];
-            const double i2 = I * I, k2 = K * K;
-            const double norm = std::sqrt(i2 + k2);                                         // :578
-            const double d = norm - c;
-            const double t1 = gradient * (d * d) + 2;
-            const double u = ((I + v.rlim) + 2 * v.resZ);
-            b[T.oN + (size_t)i * T.nZ + k] = norm;
-            b[T.oV + (size_t)i * T.nZ + k] = t1 + 4 * u;                                   // :590
-        }
-    for (int ti = 0; ti < 100; ++ti) {                                                      // :674-676
-        const double theta = 3.141592653589793 * (-100 + 2 * ti) / 180;
-        b[T.oct + ti] = std::cos(theta);
-        b[T.ost + ti] = std::sin(theta);
-    }
-    for (int si = 0; si < 90; ++si) {                                                       // :679-681
-        const double sigma = 3.141592653589793 * (-90 + 2 * si) / 180;
-        b[T.ocs + si] = std::cos(sigma);
-        b[T.oss + si] = std::sin(sigma);
-    }
-    np_linspace(0.0, tunnelRad, T.nK, b + T.oks);                                           // :684
-    for (int k = 0; k < T.nK; ++k) {
-        const double d = b[T.oks + k] - c;
-        b[T.ovc + k] = gradient * (d * d) + 2;                                              // :703
-    }
-}
-
-}  // namespace
-
-// arm_obst_columns' flag: bit 1 a NaN / inf height (:334 raises), bit 0 an index below -sZ (:341 / :346)
-static int arm_obst_bad(eik_ctx* c, unsigned bad) {
-    if (bad & 2u) return set_err(c, EIK_ERR_ARG, "GetObstMap: a height is NaN or infinite (the reference raises)");
-    return set_err(c, EIK_ERR_ARG, "GetObstMap: a surface index below -sZ (the reference raises IndexError)");
-}
-
-// Build the volume on the device into d_cost (fmap * tunnel) and/or return the pieces.  d_fmap:
-// GetObstMap's finalMap (computed here when d_Z != nullptr); d_tunnel: TunnelCost's map.
-static int arm_volume_dev(eik_ctx* c, const double* d_Z, const double* d_obst, int64_t m, int64_t n,
-                          const double* gamma2D, const double* heading, int64_t npts, const eik_arm_volume* v,
-                          double* d_fmap, double* d_omap, double* d_gmap, double* d_tunnel, double* d_cost,
-                          hipStream_t st) {
-    const int64_t nc = v->sX * v->sY * v->sZ;
-    // int(round(.)) of a NaN / inf raises in the reference (:558-560 and their repeats), and so does
-    // math.cos of an inf (:531-536).  Every event converts its node, so one such input fails the call;
-    // nothing is launched for it.  (A finite input whose node overflows to inf is left to the kernel.)
-    for (int64_t k = 0; k < 3 * npts; ++k)
-        if (!std::isfinite(gamma2D[k]) || !std::isfinite(heading[k]))
-            return set_err(c, EIK_ERR_ARG, "TunnelCost: base point or heading %ld is NaN or infinite (the reference raises)",
-                           (long)(k / 3));
-    HIPCHK(c, c->misc.ensure(64));
-    HIPCHK(c, hipMemsetAsync(c->misc.p, 0, 2 * sizeof(unsigned), st));  // [0] GetObstMap, [1] TunnelCost
-    if (d_Z) {
-        HIPCHK(c, arm_obst_map(d_Z, d_obst, m, n, v->resX, v->resY, v->resZ, v->sX, v->sY, v->sZ, v->xm, v->ym, d_fmap,
-                               d_omap, d_gmap, (unsigned*)c->misc.p, st));
-    }
-    if (!d_tunnel) return EIK_OK;
-    ArmTables T;
-    arm_tables(gamma2D, heading, npts, *v, T);
-    ArmArgs a{};
-    a.sX = v->sX;
-    a.sY = v->sY;
-    a.sZ = v->sZ;
-    a.resX = v->resX;
-    a.resY = v->resY;
-    a.resZ = v->resZ;
-    a.rlim = v->rlim;
-    a.rad = T.rad;
-    a.nX = T.nX;
-    a.nZ = T.nZ;
-    a.nK = T.nK;
-    a.nA = 2ull * (unsigned long long)npts * T.nX * T.nZ;
-    a.nB = (unsigned long long)T.nX * T.nZ;
-    a.nC = 100ull * 90ull * (unsigned long long)(T.nK + 1);
-    if (a.nA + a.nB + a.nC >= 0xffffffffull) return set_err(c, EIK_ERR_ARG, "too many tunnel events");
-    for (int k = 0; k < 3; ++k) {
-        a.fw[k] = v->final_wp[k];
-        a.iw[k] = v->initial_wp[k];
-    }
-    // scratch: tables | first (u32) | closed (u8)
-    const size_t tb = sizeof(double) * T.buf.size();
-    const size_t need = tb + sizeof(unsigned) * nc + nc + 256;
-    HIPCHK(c, c->arm.ensure(need));
-    char* p = (char*)c->arm.p;
-    HIPCHK(c, hipMemcpyAsync(p, T.buf.data(), tb, hipMemcpyHostToDevice, st));
-    const double* d = (const double*)p;
-    a.toaA = d + T.oA;
-    a.toaB = d + T.oB;
-    a.toaC = d + T.oC;
-    a.tabI = d + T.oI;
-    a.tabK = d + T.oK;
-    a.norm = d + T.oN;
-    a.valA = d + T.oV;
-    a.ct = d + T.oct;
-    a.st = d + T.ost;
-    a.cs = d + T.ocs;
-    a.ss = d + T.oss;
-    a.ks = d + T.oks;
-    a.valC = d + T.ovc;
-    a.first = (unsigned*)(p + ((tb + 255) & ~(size_t)255));
-    a.closed = (unsigned char*)(a.first + nc);
-    a.tunnel = d_tunnel;
-    a.fmap = d_fmap;
-    a.out = d_cost;
-    a.bad = (unsigned*)c->misc.p + 1;
-    HIPCHK(c, arm_tunnel(a, st));
-    // the tables must outlive the kernels: T.buf is host memory copied above; wait before return
-    HIPCHK(c, hipStreamSynchronize(st));
-    unsigned bad[2] = {0, 0};
-    HIPCHK(c, hipMemcpy(bad, c->misc.p, sizeof bad, hipMemcpyDeviceToHost));
-    if (bad[0]) return arm_obst_bad(c, bad[0]);
-    if (bad[1]) return set_err(c, EIK_ERR_ARG, "TunnelCost: a node index is infinite (the reference raises OverflowError)");
-    return EIK_OK;
-}
-
-static int arm_check(eik_ctx* c, const eik_arm_volume* v) {
-    if (!v || v->sX < 1 || v->sY < 1 || v->sZ < 1 || !(v->resX > 0) || !(v->resY > 0) || !(v->resZ > 0))
-        return set_err(c, EIK_ERR_ARG, "bad arm volume");
-    if (v->sX != v->sY) return set_err(c, EIK_ERR_ARG, "arm volume must be square in x, y (sX %ld != sY %ld)",
-                                       (long)v->sX, (long)v->sY);
-    return EIK_OK;
-}
-
-extern "C" {
-
-int eik_arm_obst_map_f64(eik_ctx* c, const double* Z, const double* obst, int64_t m, int64_t n,
-                         const eik_arm_volume* v, double* fmap, double* omap, double* gmap) {
-    if (!c || !Z || !obst || !fmap || m < 1 || n < 1) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    int rc = arm_check(c, v);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int64_t nc = v->sX * v->sY * v->sZ, nz = m * n;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * (2 * nz + 3 * nc)));
-    double* dZ = (double*)c->T2.p;
-    double* dO = dZ + nz;
-    double* dF = dO + nz;
-    double* dOm = omap ? dF + nc : nullptr;
-    double* dGm = gmap ? dF + 2 * nc : nullptr;
-    HIPCHK(c, host_to_dev(c, dZ, Z, sizeof(double) * nz, st));
-    HIPCHK(c, host_to_dev(c, dO, obst, sizeof(double) * nz, st));
-    rc = arm_volume_dev(c, dZ, dO, m, n, nullptr, nullptr, 0, v, dF, dOm, dGm, nullptr, nullptr, st);
-    if (rc) return rc;
-    unsigned bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, c->misc.p, sizeof bad, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, dev_to_host(c, fmap, dF, sizeof(double) * nc, st));
-    if (omap) HIPCHK(c, dev_to_host(c, omap, dOm, sizeof(double) * nc, st));
-    if (gmap) HIPCHK(c, dev_to_host(c, gmap, dGm, sizeof(double) * nc, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    if (bad) return arm_obst_bad(c, bad);
-    return EIK_OK;
-}
-
-int eik_arm_tunnel_cost_f64(eik_ctx* c, const double* gamma2D, const double* heading, int64_t npts,
-                            const eik_arm_volume* v, double* Cmap) {
-    if (!c || !gamma2D || !heading || !Cmap || npts < 1) return c ? set_err(c, EIK_ERR_ARG, "NULL argument") : EIK_ERR_ARG;
-    int rc = arm_check(c, v);
-    if (rc) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t nc = v->sX * v->sY * v->sZ;
-    HIPCHK(c, c->T2.ensure(sizeof(double) * nc));
-    double* dT = (double*)c->T2.p;
-    rc = arm_volume_dev(c, nullptr, nullptr, 0, 0, gamma2D, heading, npts, v, nullptr, nullptr, nullptr, dT, nullptr,
-                        c->stream);
-    if (rc) return rc;
-    HIPCHK(c, dev_to_host(c, Cmap, dT, sizeof(double) * nc, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return EIK_OK;
-}
-
-int eik_arm_path_f64(eik_ctx* c, const double* Z, const double* obst, int64_t m, int64_t n, const double* gamma2D,
-                     const double* heading, int64_t npts, const eik_arm_volume* v, double tau, double* path,
-                     int64_t cap, int64_t* n_out, int* status, double* cost_out, double* T_out) {
-    if (!c || !Z || !obst || !gamma2D || !heading || !path || !n_out || !status || npts < 1 || m < 1 || n < 1 ||
-        !(tau > 0) || cap < 2)
-        return c ? set_err(c, EIK_ERR_ARG, "bad arm-path arguments") : EIK_ERR_ARG;
-    int rc = arm_check(c, v);
-    if (rc) return rc;
-    for (int k = 0; k < 3; ++k) {
-        const int64_t lim = k == 0 ? v->sX : k == 1 ? v->sY : v->sZ;
-        if ((int64_t)v->final_wp[k] >= lim || (int64_t)v->initial_wp[k] >= lim)
-            return set_err(c, EIK_ERR_ARG, "waypoint outside the %ldx%ldx%ld volume", (long)v->sX, (long)v->sY,
-                           (long)v->sZ);
-    }
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const int64_t nc = v->sX * v->sY * v->sZ, nz = m * n;
-    const int64_t steps = (int64_t)std::nearbyint(15000.0 / tau);
-    const int64_t pcap = std::min<int64_t>(cap, steps + 4);
-    // Z | obst | fmap | tunnel | cost | T (full) | T (early exit) | path | n_out | status
-    HIPCHK(c, c->T2.ensure(sizeof(double) * (2 * nz + 5 * nc + 3 * pcap) + 64));
-    double* dZ = (double*)c->T2.p;
-    double* dO = dZ + nz;
-    double* dF = dO + nz;
-    double* dTun = dF + nc;
-    double* dC = dTun + nc;
-    double* dTf = dC + nc;
-    double* dT = dTf + nc;
-    double* dP = dT + nc;
-    int64_t* dn = (int64_t*)(dP + 3 * pcap);
-    int* dst = (int*)(dn + 1);
-    HIPCHK(c, host_to_dev(c, dZ, Z, sizeof(double) * nz, st));
-    HIPCHK(c, host_to_dev(c, dO, obst, sizeof(double) * nz, st));
-    rc = arm_volume_dev(c, dZ, dO, m, n, gamma2D, heading, npts, v, dF, nullptr, nullptr, dTun, dC, st);
-    if (rc) return rc;
-    // FM3D.computeTmap(Cmap, finalWayPointArm, initialWayPointArm) :1585; H = sY rows, W = sX columns
-    // with its early exit once initialWayPointArm is popped (FastMarching3D.py:141)
-    const int64_t goal[3] = {v->final_wp[0], v->final_wp[1], v->final_wp[2]};
-    const int64_t start[3] = {v->initial_wp[0], v->initial_wp[1], v->initial_wp[2]};
-    rc = fim3d_solve_one(c, dC, dTf, v->sY, v->sX, v->sZ, EIK_F64, goal, st,
-                         early_offset(goal, start, v->sY, v->sX, v->sZ));
-    if (rc) return rc;
-    rc = eik_fim3d_early_exit(c, dC, dTf, dT, v->sY, v->sX, v->sZ, EIK_F64, goal, start, st);
-    if (rc) return rc;
-    // FM3D.getPathGDM(Tmap3D, initialWayPointArm, finalWayPointArm, 0.5) :1588
-    const double init[3] = {(double)v->initial_wp[0], (double)v->initial_wp[1], (double)v->initial_wp[2]};
-    const double end[3] = {(double)v->final_wp[0], (double)v->final_wp[1], (double)v->final_wp[2]};
-    rc = eik_path3d_dev(c, dT, EIK_F64, v->sY, v->sX, v->sZ, init, end, tau, dP, pcap, dn, dst, st);
-    if (rc) return rc;
-    int64_t hn = 0;
-    HIPCHK(c, hipMemcpyAsync(&hn, dn, sizeof hn, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(status, dst, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    *n_out = hn;
-    HIPCHK(c, hipMemcpyAsync(path, dP, sizeof(double) * 3 * hn, hipMemcpyDeviceToHost, st));
-    if (cost_out) HIPCHK(c, dev_to_host(c, cost_out, dC, sizeof(double) * nc, st));
-    if (T_out) HIPCHK(c, dev_to_host(c, T_out, dT, sizeof(double) * nc, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    return EIK_OK;
 }
 
 int eik_tmap3d_batch_f64(eik_ctx* c, const double* cost, int64_t B, int64_t H, int64_t W, int64_t L,

@@ -1,4 +1,5 @@
-"""The kernel launches behind the goal and seed-set entry points of csrc/eikonal_api.cpp, to compare two
+"""The kernel launches behind the entry points of csrc/api_*.cpp (solves and re-solves from goals and seed sets,
+paths, the bidirectional fronts, the 3D solvers, the cost builder), to compare two
 builds of libeikonal.so launch for launch (a host-side refactor must leave the sequence as it was).
 
     EIKONAL_LIB=<a> rocprofv3 --kernel-trace --output-format csv -d A -- python tools/launch_sequence.py
@@ -71,6 +72,16 @@ def calls():
         Ts = c.tmap2d_seeds(cost, seeds, t0, dtype=dt, labels=True)[0]
         c.tmap2d_update_seeds(new, Ts, seeds, t0, rect, seeds_new=moved, t0_new=t0, dtype=dt, labels=True)
         c.tmap2d_update_seeds(new, Ts, seeds, t0, rect, dtype=dt)
+        # paths on that field: the walker, the obstacle-safe one, a batch; the batched plan on two maps
+        c.path2d(T, (150, 160), goal)
+        c.path2d_safe(T, (150, 160), goal)
+        c.path2d_batch(T, [(150, 160), (100, 5)], goal)
+        c.plan2d_batch(np.stack([cost, new]), [goal, goal], [(150, 160), (100, 5)])
+        if dt is np.float64:  # the bidirectional fronts: the band relaxation, then the exact replay
+            for exact in (0, 1):
+                c.set_option(L.OPT_EXACT_BAND, exact)
+                c.tmap2d_bidir(cost, goal, (150, 160))
+            c.set_option(L.OPT_EXACT_BAND, 0)
         # 3D: the general and the layered solver from a goal and from seeds, the labels, the list mode
         vol, flat = rng.uniform(1, 10, (20, 20, 12)).astype(dt), rng.uniform(1, 10, (70, 70, 3)).astype(dt)
         s3, f3 = [(3, 4, 5), (15, 16, 2)], [(10, 12, 0), (60, 50, 2)]
@@ -83,6 +94,11 @@ def calls():
             c.tmap3d_seeds(vol, s3, [0.0, 2.5], dtype=dt, labels=True)
             c.tmap3d_seeds(flat, f3, [0.0, 2.5], dtype=dt, labels=True)
             assert c.last_solver3d()["layered"] == layered
+        # the early exit, a 3D path, a batch of volumes; the cost builder on a random surface
+        c.tmap3d(vol, (3, 4, 5), dtype=dt, start=(15, 16, 2))
+        c.path3d(Tv, (15, 16, 2), (3, 4, 5))
+        c.tmap3d_batch(np.stack([vol, vol]), [(3, 4, 5), (15, 16, 2)])
+        c.costmap(0.02 * rng.random((190, 170)), 0.05, 0.05 * 190)
         c.set_option(L.OPT_MODE, L.MODE_LIST)
         c.tmap3d(vol, (3, 4, 5), dtype=dt)
         c.close()
